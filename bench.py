@@ -15,8 +15,12 @@ would produce) and `--lanes` chains (default: 1..3, chosen from K) are kept in f
 (llamagen_amd/pipeline.py: the decode chain is latency-bound, chains interleave on the chip); all K timed steps start and
 finish inside the timed region.  N > 1 shards independent images over ranks (weak scaling, no collective during
 generation) and ends every step with ONE RCCL gather of the decoded batch to rank 0.  Rank 0 prints
-one JSON line with `roofline` (dominant kernel = decode attention, measured live with HIP events on
-its launch stream) and `cpu_baseline` (the CPU oracle / reference timed on a bounded sample).
+one JSON line (`metric`, `value`, `unit`, `ms_per_step`, ...).  A plain run does only that: set up, warm up, time the K steps,
+print.  `--full` adds the legs outside the timed region: `roofline` (dominant kernel = decode attention, measured live with HIP
+events on its launch stream), `roofline_gemm`, `roofline_vq_decode`, live PMC traffic, the one-chain / one-step transparency legs,
+`other_configs` (configs 3-5 in child processes) and `cpu_baseline` (the CPU oracle / reference timed on a bounded sample);
+the `--no-*` options drop single legs of a `--full` run.  `--dump-outputs DIR` writes what the last timed step returned
+(`images.npy`: the uint8 HWC batch gathered to rank 0; `tokens.npy`: rank 0's token ids of that batch), as float32.
 """
 import argparse
 import json
@@ -476,6 +480,30 @@ def other_configs(timeout_s=420):
     return out
 
 
+DUMP_BUDGET_BYTES = 64e6
+
+
+def dump_outputs(out_dir, images, ids):
+    """--dump-outputs: what the last timed step returned, as float32 .npy files (both exact in float32): `images` = the uint8
+    HWC batch gathered to rank 0 (B x n_gpus, img, img, 3), `tokens` = rank 0's token ids of that batch (B, tokens per image).
+    When the images would not fit DUMP_BUDGET_BYTES (e.g. --config 4, --gpus 8), a fixed seeded sample of whole images is kept
+    and `images_index` names the rows it holds."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    tokens = ids.detach().cpu().numpy().astype(np.float32)
+    imgs = images.detach().cpu().numpy()
+    per_image = imgs[0].size * 4
+    keep = int((DUMP_BUDGET_BYTES - tokens.nbytes) // per_image)
+    arrays = {"tokens": tokens}
+    if keep < imgs.shape[0]:
+        index = np.sort(np.random.default_rng(0).choice(imgs.shape[0], keep, replace=False))
+        imgs = imgs[index]
+        arrays["images_index"] = index.astype(np.float32)
+    arrays["images"] = imgs.astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -551,9 +579,15 @@ def main():
     ap.add_argument("--budget-check-only", action="store_true", help="plan the schedule, check the per-GPU HBM budget, print it, exit")
     ap.add_argument("--allow-untested-schedule", action="store_true", help="run a GEMM schedule no end-to-end parity test names")
     ap.add_argument("--no-one-chain", action="store_true", help="skip the extra one-chain-in-flight leg (it needs another chain's KV slabs)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short passes of BASELINE configs 4 and 5 (default config-2 run)")
+    ap.add_argument("--no-other-configs", action="store_true", help="skip the short passes of BASELINE configs 3-5 (--full config-2 run)")
+    ap.add_argument("--full", action="store_true", help="also run every leg outside the timed region (rooflines, live PMC traffic, "
+                                                        "one-chain / one-step legs, other_configs, cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy (float32)")
     ap.add_argument("--standin", action="store_true", help=argparse.SUPPRESS)  # CPU/gloo test of the launch path, see standin_main
     args = ap.parse_args()
+    if not args.full:   # a plain run: set up, warm up, time the steps, print -- nothing outside the timed region
+        args.no_cpu_baseline = args.no_roofline = args.no_live_traffic = args.no_solo = args.no_one_chain = True
+        args.no_other_configs = True
 
     if args.budget_check_only:   # no device, no model: the plan and its HBM need
         C0 = CONFIGS[args.config]
@@ -620,9 +654,13 @@ def main():
 
     from llamagen_amd.postprocess import to_uint8_hwc
 
+    step_ids = {}
+
     def finish(job_id, idx, im):
         """Per batch, enqueued on its lane's stream as soon as decode_code() is: fp32 [-1, 1] -> uint8 HWC (what the
         reference writes out, sample_c2i_ddp.py:143) and the step's ONE collective (uint8 gather to rank 0)."""
+        if args.dump_outputs:
+            step_ids[job_id] = idx   # this rank's token ids of the batch (for --dump-outputs)
         return ldist.gather_to_root(to_uint8_hwc(im))
 
     def make_cond():
@@ -650,6 +688,8 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs[-1], step_ids[args.steps - 1])
 
     # transparency: the same workload with ONE chain in flight (2 chains, one after the other, on a lane of their own with the
     # single-chain GEMM shapes), outside the timed region above
@@ -689,9 +729,9 @@ def main():
                           "steps_in_flight_per_gpu": args.lanes * bpc},
                # SURVEY 8d closed form for ONE generate() of this config's batch (per GPU)
                "algorithmic_bytes_per_generate": {k: int(v) for k, v in phase.items()},
-               # the same workload with ONE chain (bpc batches) in flight at a time (no cross-chain overlap)
-               "images_per_s_with_one_chain_in_flight": round(chain1, 3),
                "gemm_schedule": {"schedule": gsched0, "source": sched_source, "tested_end_to_end": sched_tested}}
+        if args.full:   # the same workload with ONE chain (bpc batches) in flight at a time (no cross-chain overlap)
+            res["images_per_s_with_one_chain_in_flight"] = round(chain1, 3)
         total_b = sum(phase[k] for k in ("weights", "kv_reads", "kv_writes", "logits", "noise"))
         res["gpt_phase_floor_ms_per_step_at_8TBps"] = round(total_b / 8e12 * 1e3, 1)
         pmc = {}

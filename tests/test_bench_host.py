@@ -135,3 +135,24 @@ def test_config2_schedules_only_tested_chain_widths():
     assert bench.plan_schedule(a, 16, 1024, 120)[0] == 8 and a.lanes == 2
     a = argparse.Namespace(config=5, steps=24, batches_per_chain=0, lanes=0, no_one_chain=True)      # what other_configs() runs: 2 x 12 = 384 rows
     assert bench.plan_schedule(a, 16, 1024, 120)[0] == 12 and a.lanes == 2
+
+
+def test_dump_outputs_writes_float32_within_budget(tmp_path):
+    """--dump-outputs: the last step's uint8 images and token ids as exact float32 .npy files; a batch over the 64 MB budget keeps a
+    fixed seeded sample of whole images (the same one every time) and names its rows in images_index."""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(0)
+    ids = torch.randint(0, 16384, (32, 576), generator=g)
+    imgs = torch.randint(0, 256, (32, 384, 384, 3), dtype=torch.uint8, generator=g)
+    bench.dump_outputs(str(tmp_path / "a"), imgs, ids)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sorted(got) == ["images", "tokens"] and all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["images"], imgs.numpy()) and np.array_equal(got["tokens"], ids.numpy())
+    big = torch.randint(0, 256, (64, 384, 384, 3), dtype=torch.uint8, generator=g)     # --config 4: batch 64
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big, ids)
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= bench.DUMP_BUDGET_BYTES
+    idx = np.load(tmp_path / "b" / "images_index.npy")
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "images_index.npy")) and len(set(idx.tolist())) == len(idx) > 0
+    assert np.array_equal(np.load(tmp_path / "b" / "images.npy"), big.numpy()[idx.astype(np.int64)])
