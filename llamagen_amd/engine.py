@@ -16,6 +16,8 @@ from typing import Optional
 import torch
 
 from . import _lib as L
+from . import gemm_schedule as S
+from .gemm_schedule import MODEL_TILE_SCHEDULES, TESTED_TILE_SCHEDULES, TILE_SCHEDULES, tile_schedule_key  # noqa: F401  (the tests name them here)
 
 
 def _ceil_div(a, b):
@@ -59,98 +61,6 @@ def precompute_freqs_cis_2d(grid_size: int, n_elem: int, base: float, cls_token_
     fg = torch.concat([freqs[:, None, :].expand(-1, grid_size, -1), freqs[None, :, :].expand(grid_size, -1, -1)], dim=-1)
     cache = torch.stack([torch.cos(fg), torch.sin(fg)], dim=-1).flatten(0, 1)
     return torch.cat([torch.zeros(cls_token_num, n_elem // 2, 2), cache])
-
-
-# Big-M tile family (csrc/gemm_tile.hip): workgroup shapes (wm, wn, mtv, ntv, kb, stages, lw) per decode GEMM, keyed by the smallest
-# MTs (rows / 16) they serve.  Per-CU tile area ~ rows x N / 256 CUs, as square as the wave arrangement allows (the feed per CU is the
-# tile perimeter x K); measured on MI355X with tools/gemm_tile_sweep.py (gpurun_out/tile_sweep2/3.log, GPT-L, us per launch,
-# skinny -> tile): 256 rows wqkv 10.2 -> 9.8, wo 4.85 -> 4.1, w1||w3 13.1 -> 10.6, w2 7.8 -> 7.7, lm_head 23.2 -> 20.9; 512 rows
-# 16.3 -> 12.9, 7.7 -> 5.1, 20.3 -> 18.9, 9.5 -> 7.9, 39.0 -> 37.8; 1024 rows 51.6 -> 22.1, 13.0 -> 6.6, 34.1 -> 35.0, 16.9 -> 11.5,
-# 71.1 -> 68.8.  The 256- and 640-row tables are what tests/test_gpu_headline.py holds to the oracle end to end and what bench.py
-# accepts as a tested schedule; every shape of every table is held to the oracle at kernel level (and all shapes agree bit for bit).
-TILE_SCHEDULES = {
-    16: {"qkv": (4, 1, 1, 3, 4, 4, 4), "wo": (2, 2, 1, 1, 4, 4, 4), "w13": (4, 1, 1, 6, 4, 3, 4), "w2": (2, 2, 1, 1, 4, 4, 4),
-         "head": (4, 1, 2, 8, 2, 4, 4)},
-    32: {"qkv": (4, 1, 1, 6, 4, 3, 4), "wo": (2, 2, 2, 1, 4, 4, 4), "w13": (4, 1, 2, 8, 2, 4, 4), "w2": (2, 2, 2, 1, 4, 4, 4),
-         "head": (4, 1, 2, 8, 2, 4, 4)},
-    # 640 rows (`bench.py --steps 20`: two chains of ten batches), gpurun_out/tile_sweep4.log: a launch is whole ROUNDS of <= 256
-    # workgroups, so the shapes are the ones that fill one round -- wqkv 240 workgroups 16.0 us (22.1 with the 512-row shape: 320
-    # workgroups = two rounds), wo 160 / 6.3 (8.1), w1||w3 220 / 18.2, w2 160 / 10.9 (14.6), lm_head 640 / 50.3
-    # (w1||w3 and lm_head: eight consumer waves x one m-tile -- two per SIMD, one's RMSNorm VALU work under the other's MFMAs:
-    # 18.2 against 19.2 us and 50.3 against 52.0 for four waves x two m-tiles, gpurun_out/tile_sweep5.log)
-    40: {"qkv": (4, 1, 1, 8, 2, 4, 4), "wo": (2, 2, 2, 2, 4, 4, 4), "w13": (8, 1, 1, 8, 2, 4, 4), "w2": (2, 2, 2, 2, 4, 4, 4),
-         "head": (8, 1, 1, 8, 2, 4, 4)},
-    64: {"qkv": (4, 1, 2, 8, 2, 4, 4), "wo": (2, 2, 2, 2, 4, 4, 4), "w13": (4, 1, 2, 8, 2, 4, 4), "w2": (2, 2, 2, 2, 4, 4, 4),
-         "head": (4, 1, 2, 8, 2, 4, 4)},
-}
-TILE_SCHEDULE_EXACT = (40,)        # keys that serve exactly that MTs; the others serve every MTs from the key up to the next one
-TESTED_TILE_SCHEDULES = (16, 40)   # keys of TILE_SCHEDULES with an end-to-end oracle test (tests/test_gpu_headline.py)
-TABLE_MODEL = (1024, 2816, 16384)   # (dim, ffn hidden, vocab) of GPT-L: the model TILE_SCHEDULES was measured on
-
-# The other registry models that bench.py runs with chains of >= 256 rows: the shapes the round-4 on-device search settled on
-# (profiles/r04_bench_config{3,4}.json, `schedule`), now PINNED.  Round 4 timed every shape (and the skinny kernel) at first use in
-# the user's process and kept whichever was faster at that moment: the tile shapes agree bit for bit, but tile and skinny differ in
-# accumulation order and in the SwiGLU's exp / reciprocal, so the family -- and with it bf16 logits -- depended on timing noise
-# (ADVICE round 4).  The family now depends on shapes only: tile wherever a table names a shape the library takes.
-MODEL_TILE_SCHEDULES = {
-    TABLE_MODEL: TILE_SCHEDULES,
-    # Round 6: chains of >= 512 rows for the wide models (bench.py --config 3 / 4: two chains of eight batches of 32 / four batches of
-    # 64) with shapes MEASURED per model and width (tools/gemm_tile_sweep.py, profiles/r06_tile_sweep_{xxl,3b,xl}.log, us per launch):
-    # GPT-XXL 512 rows wqkv 24.0 (28.9 with the 256-row shape), w1||w3 26.1, wo 8.4, w2 19.6, lm_head 50.5; GPT-3B 512 rows wqkv 99.4,
-    # w1||w3 140.7 (153.3), wo 23.7 (32.8), w2 53.6 (75.0), lm_head 109.3 (114.8); GPT-XL 256 rows (config 5: two chains of eight
-    # batches of 16) wqkv 12.8 (skinny 15.4), wo 5.6 (7.3), w1||w3 14.8 (20.0), w2 13.3 (12.6), lm_head 24.5 (27.1).
-    (1536, 4096, 16384): {   # GPT-XXL (config 3)
-        16: {"qkv": (4, 1, 1, 8, 2, 4, 4), "wo": (2, 2, 2, 2, 4, 4, 4), "w13": (4, 1, 2, 8, 2, 4, 4), "w2": (2, 2, 2, 2, 4, 4, 4),
-             "head": (4, 1, 2, 8, 2, 4, 4)},
-        # wqkv: four consumer waves x two m-tiles instead of eight x one -- 25.5 against 24.0 us alone, 47.5 against 45.6 / 46.0 img/s in
-        # the two-chain bench (same box, profiles/r06_c3_c5_shape_ab.log; the other candidates of that log lose or tie)
-        32: {"qkv": (4, 1, 2, 6, 2, 4, 4), "wo": (2, 2, 2, 2, 4, 4, 4), "w13": (4, 1, 2, 8, 2, 4, 4), "w2": (2, 2, 2, 2, 4, 4, 4),
-             "head": (4, 1, 2, 8, 2, 4, 4)}},
-    (3200, 8704, 16384): {   # GPT-3B (config 4)
-        16: {"qkv": (8, 1, 1, 6, 2, 4, 4), "wo": (2, 2, 2, 2, 4, 4, 4), "w13": (4, 1, 1, 6, 2, 4, 4), "w2": (2, 2, 2, 2, 4, 4, 4),
-             "head": (8, 1, 1, 8, 2, 4, 4)},
-        # 512 rows, statistics grouped (lgen_ssq_group4): wqkv 128 x 160 tiles = 240 workgroups, ONE round of the 256 CUs, 53.3 us
-        # (75.3 with 128 x 96 = 400 workgroups = two rounds; 98.9 before the grouping: profiles/r06_tile_sweep2_3b.log).  w1||w3 keeps
-        # 128 x 96: the 128 x 160 shape is faster alone (90.1 against 102.9 us) and SLOWER in the two-chain bench -- same box,
-        # alternating (profiles/r06_c4_shape_ab.log): both new 31.4 / 31.4, both old 36.0 / 35.8, new wqkv only 37.2, new w1||w3 only 31.3 img/s
-        32: {"qkv": (4, 1, 2, 10, 2, 4, 4), "wo": (2, 2, 4, 2, 2, 4, 4), "w13": (4, 1, 2, 6, 2, 4, 4), "w2": (2, 2, 4, 2, 2, 4, 4),
-             "head": (4, 1, 2, 8, 2, 4, 4)}},
-    (1280, 3584, 16384): {   # GPT-XL (config 5, t2i)
-        16: {"qkv": (4, 1, 1, 4, 4, 4, 4), "wo": (2, 2, 2, 1, 4, 4, 4), "w13": (4, 1, 1, 8, 2, 4, 4), "w2": (2, 2, 2, 1, 4, 4, 4),
-             "head": (8, 1, 1, 8, 2, 4, 4)},
-        # 384 rows (two chains of twelve batches of 16, what bench.py --config 5 runs): 64 x 64 wqkv tiles would be 360 workgroups (two
-        # rounds of the 256 CUs), 64 x 128 w1||w3 tiles 336; 64 x 96 (240) and 128 x 128 (168) fill one -- 21.6 / 21.45 against 21.16 /
-        # 21.25 img/s in the two-chain bench, same box, alternating (profiles/r06_c5_shape_ab2.log)
-        24: {"qkv": (4, 1, 1, 6, 4, 3, 4), "wo": (2, 2, 2, 1, 4, 4, 4), "w13": (4, 1, 2, 8, 2, 4, 4), "w2": (2, 2, 2, 1, 4, 4, 4),
-             "head": (8, 1, 1, 8, 2, 4, 4)}},
-}
-# (dim, F, V) -> keys of its table that an end-to-end oracle test runs (tests/test_gpu_headline.py:
-# test_config{3,4}_..._shapes_bf16_vs_oracle[128] / [192]: 256- / 384-row chains; test_config{3,4,5}_wide_chain_shapes_bf16_vs_oracle:
-# the 512- / 512- / 256-row chains bench.py runs since round 6)
-TESTED_MODEL_SCHEDULES = {TABLE_MODEL: TESTED_TILE_SCHEDULES, (1536, 4096, 16384): (16, 32), (3200, 8704, 16384): (16, 32),
-                          (1280, 3584, 16384): (16, 24)}
-
-
-def tile_schedule_key(mts: int, table=None):
-    """Key of a tile table (default TILE_SCHEDULES) that serves a chain of `mts` m-tiles (None: below 256 rows, the skinny kernels)."""
-    table = TILE_SCHEDULES if table is None else table
-    exact = TILE_SCHEDULE_EXACT if table is TILE_SCHEDULES else ()
-    if mts in exact:
-        return mts
-    keys = [k for k in table if k not in exact and k <= mts]
-    return max(keys) if keys else None
-
-
-# Every workgroup shape the library instantiates (csrc/gemm_tile.hip GT_SHAPES_NORM / GT_SHAPES_PLAIN): the candidates
-# of the opt-in on-device shape search below (LGEN_TILE_AUTOTUNE=1).  All shapes of the family produce bit-identical results (one
-# wave accumulates an output element over k in order, whatever the tiling: tests/test_gpu_headline.py), and the search never leaves
-# the family, so it only ever changes the speed.
-TILE_SHAPES_NORM = ((4, 1, 1, 3, 4, 4, 4), (4, 1, 1, 4, 4, 4, 4), (4, 1, 1, 6, 2, 4, 4), (4, 1, 1, 6, 4, 3, 4), (4, 1, 1, 8, 2, 4, 4),
-                    (4, 1, 2, 4, 2, 4, 4), (4, 1, 2, 6, 2, 4, 4), (4, 1, 2, 8, 2, 4, 4), (4, 1, 1, 2, 4, 4, 4), (8, 1, 1, 8, 2, 4, 4),
-                    (8, 1, 1, 6, 2, 4, 4), (8, 1, 1, 4, 2, 4, 4), (4, 1, 2, 10, 2, 4, 4))
-TILE_SHAPES_PLAIN = ((2, 2, 1, 1, 4, 4, 4), (2, 2, 1, 2, 4, 4, 4), (2, 2, 2, 1, 4, 4, 4), (2, 2, 2, 2, 4, 4, 4), (2, 2, 2, 2, 2, 4, 4),
-                     (4, 1, 1, 2, 4, 4, 4), (2, 2, 4, 1, 4, 4, 4), (2, 2, 4, 2, 2, 4, 4))
-_TUNED = {}   # (device index, dim, F, V, n_head, MTs, per-row positions?) -> {kind: shape | None}: one search per process, shared by every lane
 
 
 class PackedWeights:
@@ -219,15 +129,7 @@ class DecodeEngine:
                                       "columns (use --precision none, or a model width the fused-norm GEMMs take)")
         if self.V % 16:
             raise NotImplementedError("vocab_size must be a multiple of 16")
-        mts = _ceil_div(max_batch, 16)
-        if mts > 8:
-            mts = _ceil_div(mts, 8) * 8
-        elif mts > 4:
-            mts = 8
-        elif mts == 3:
-            mts = 4
-        self.MTs = mts
-        self.mt = min(mts, 4)  # m-tiles per workgroup (1, 2 or 4; MTs is 1, 2, 4 or a multiple of 8)
+        self.MTs = mts = S.round_mts(max_batch)
         dev, dt = self.dev, dtype
         z = lambda *s, dtype=dt: torch.zeros(*s, dtype=dtype, device=dev)
         # KV slabs (gpt.py:170-185); hd padded to 64/128 so a key row is a power-of-two lane group.  Two separate
@@ -281,54 +183,14 @@ class DecodeEngine:
         self._graphs = {}
         self._prof = None
         self.pos_rows = None         # continuous batching (llamagen_amd/serve.py): int32 [MTs*16] per-row positions
-        # RMSNorm folded into the consumer GEMMs (5 launches / layer instead of 7).  Pays off (-12 % step time,
-        # GPT-L) only with gemm_normpre.hip, which normalises the activation panel in registers while the
-        # weight loads are in flight and needs a wave's K range to fit in registers: bf16, d/32 = 8 waves x
-        # 3..6 chunks (GPT-B .. GPT-XXL).  Elsewhere the stand-alone 3.4 us norm kernels are faster than the
-        # generic NORM prologue (+4 us of exposed VALU work per GEMM).
-        kch = self.d // self.kc
-        auto = dtype == torch.bfloat16 and kch % 8 == 0 and 3 <= kch // 8 <= 6
-        self.use_tile = os.environ.get("LGEN_GEMM_TILE", "1") != "0"
-        self.tile_autotune = os.environ.get("LGEN_TILE_AUTOTUNE", "0") == "1"   # opt-in (development): time the tile shapes on the device
-        # (round 4) the big-M tile family normalises the B fragments between LDS and the MFMA, whatever the row length: chains of
-        # >= 256 rows fuse for every width whose statistics row the kernels take (GPT-3B: d = 3200, 200 partials per row)
-        self._fuse_base = auto   # what holds without the tile family (per-row positions: the wqkv of a continuous batcher stays skinny)
-        if dtype == torch.bfloat16 and self.MTs >= 16 and self.use_tile and (self.d // 16) % 4 == 0 and self.d // 16 <= L.SSQ_STRIDE:
-            auto = True
-        env = os.environ.get("LGEN_FUSED_NORM")
-        self._fuse_env, self._fuse_auto, self._fuse_forced = env, auto, None   # `fuse_norm` is DERIVED from these + pos_rows (property below)
+        self.use_tile = os.environ.get("LGEN_GEMM_TILE", "1") != "0"   # big-M tile family (round 4); 0 keeps the skinny kernels
+        # tuning hooks (gemm_schedule.env_overrides): kind ("qkv" | "wo" | "w13" | "w2" | "head") -> (mt, nt, kw) / tile shape / passes
+        self.tile_override, self.tile_shape_override, self.pass_override = S.env_overrides()
         self._tile_refused = set()   # GEMM kinds whose table shape the library refused (LGEN_ERR_UNSUPPORTED): served by the skinny kernels, reported as such
-        self.tile_override = {}      # kind ("qkv" | "wo" | "w13" | "w2" | "head") -> (mt, nt, kw)
-        # tuning hook: LGEN_TILES="qkv=2,4,8;wo=4,1,8;w2=4,1,8" (e.g. fewer, fatter workgroups per GEMM so that the
-        # kernels of several in-flight batches share the chip side by side instead of taking turns)
-        for item in filter(None, os.environ.get("LGEN_TILES", "").split(";")):
-            kind, _, val = item.partition("=")
-            if kind.strip() not in ("qkv", "wo", "w13", "w2", "head"):
-                raise ValueError(f"LGEN_TILES: unknown GEMM '{kind}'")
-            t = tuple(int(v) for v in val.split(","))
-            if len(t) != 3:
-                raise ValueError(f"LGEN_TILES: '{item}' is not kind=mt,nt,kw")
-            self.tile_override[kind.strip()] = t
-        # fused-norm GEMM schedule (the `passes` argument of lgen_gemm): kind -> (passes, 0); LGEN_PASSES="qkv=2,0;w13=3,0"
-        # big-M tile family (round 4): LGEN_GEMM_TILE=0 keeps the skinny kernels; LGEN_TILE_SHAPES="qkv=4,1,1,3,4,4,4;..." picks shapes
-        self.tile_shape_override = {}
-        for item in filter(None, os.environ.get("LGEN_TILE_SHAPES", "").split(";")):
-            kind, _, val = item.partition("=")
-            if kind.strip() not in ("qkv", "wo", "w13", "w2", "head"):
-                raise ValueError(f"LGEN_TILE_SHAPES: unknown GEMM '{kind}'")
-            t = tuple(int(v) for v in val.split(","))
-            if len(t) != 7:
-                raise ValueError(f"LGEN_TILE_SHAPES: '{item}' is not kind=wm,wn,mtv,ntv,kb,stages,lw")
-            self.tile_shape_override[kind.strip()] = t
-        self.pass_override = {}
-        for item in filter(None, os.environ.get("LGEN_PASSES", "").split(";")):
-            kind, _, val = item.partition("=")
-            if kind.strip() not in ("qkv", "w13", "head"):
-                raise ValueError(f"LGEN_PASSES: unknown fused-norm GEMM '{kind}'")
-            t = tuple(int(v) for v in val.split(","))
-            if len(t) != 2 or t[0] < 1:
-                raise ValueError(f"LGEN_PASSES: '{item}' is not kind=passes,double_buffer")
-            self.pass_override[kind.strip()] = t
+        self._plan = self._plan_facts = None
+        # `fuse_norm` is DERIVED from these + pos_rows (property below); _fuse_base: what holds with per-row positions
+        self._fuse_env, self._fuse_forced = os.environ.get("LGEN_FUSED_NORM"), None
+        self._fuse_base, self._fuse_auto = (S.fuse_norm_auto(self._schedule_inputs(), rows) for rows in (True, False))
         self._pack(model)
 
     @property
@@ -396,251 +258,70 @@ class DecodeEngine:
         self.use_mask = False
         self.causal_mask.copy_(torch.tril(torch.ones(self.S8, self.S8, dtype=torch.bool, device=self.dev)))
 
-    # ---- tile heuristics --------------------------------------------------------------------
+    # ---- GEMM schedule (llamagen_amd/gemm_schedule.py) --------------------------------------------
+    def _schedule_inputs(self) -> S.ScheduleInputs:
+        return S.ScheduleInputs(d=self.d, F=self.F, V=self.V, head_dim=self.hd, n_layer=self.L, MTs=self.MTs, dtype=self.dtype,
+                                max_kw=self.lib.lgen_gemm_max_kw, use_tile=self.use_tile, tile_override=dict(self.tile_override),
+                                tile_shape_override=dict(self.tile_shape_override), pass_override=dict(self.pass_override))
+
+    @property
+    def plan(self) -> S.Plan:
+        """Kernel family, shape, passes and statistics grouping of every decode GEMM: what the launches below, gemm_schedule(),
+        tile_schedule_tested() and launches_per_step() all read.  Recomputed only when one of the facts it depends on changed."""
+        facts = (self.fuse_norm, self._pos_rows is not None, frozenset(self._tile_refused), self.use_tile,
+                 *(tuple(sorted(o.items())) for o in (self.tile_override, self.tile_shape_override, self.pass_override)))
+        if facts != self._plan_facts:
+            self._plan = S.make_plan(self._schedule_inputs(), self.fuse_norm, self._pos_rows is not None, self._tile_refused)
+            self._plan_facts = facts
+        return self._plan
+
     def _tiles(self, kind: str, N: int, K: int):
-        """(mt, nt, kw) for one decode GEMM.  Measured on MI355X (tools/ubench_kernels.py, GPT-L, M = 64):
-        every kernel of the chain is latency-bound (~4-6 us), so the shape that wins is the one that puts
-        >= ~160 workgroups on the chip with the fewest dependent load rounds per wave: split the batch
-        rows over workgroups (mt < MTs) when N alone gives too few tiles (wo / w2: N/16 = 64), group
-        n-tiles (nt 2 / 4) only when there are >= 352 / 1024 of them (w1||w3, lm_head)."""
-        if kind in self.tile_override:
-            return self.tile_override[kind]
-        ntiles = N // 16
-        kch = K // self.kc
-        bf16 = self.dtype == torch.bfloat16
-        if self.MTs >= 8 and bf16 and not self.fuse_norm and kch >= 96:
-            # wide models (GPT-3B: d 3200, F 8704) at 256 rows: every GEMM is the plain ring kernel and the work is MFMA-shaped
-            # (64 GFLOP per layer), so big tiles and FEW K-splitting waves win -- measured (tools/gemm_sweep_wide.py,
-            # profiles/r03_wide_sweep.log): qkv (4, 4, 4) 45.0 us against (4, 2, 8) 54.7, wo (4, 4, 4) 18.2 / 26.9, w1||w3 (8, 2, 4)
-            # 64.4 / 84.1, w2 (4, 4, 8) 40.1 / 66.6, lm_head (8, 2, 4) 47.5 / 68.4: 4.07 ms of GEMMs per decode step instead of 5.64
-            # at 128 rows: qkv (4, 4, 4) 29.5 us against (4, 2, 8) 34.5, wo (4, 2, 4) 12.9 / 16.3, w1||w3 (4, 4, 4) 43.4 / 51.0,
-            # w2 (4, 2, 8) 28.8 / 37.1, lm_head (8, 2, 4) 26.3 / 36.9: 2.78 ms per step instead of 3.37
-            if self.MTs >= 16:
-                mt, nt = {"qkv": (4, 4), "wo": (4, 4), "w13": (8, 2), "w2": (4, 4), "head": (8, 2)}[kind]
-            else:
-                mt, nt = {"qkv": (4, 4), "wo": (4, 2), "w13": (4, 4), "w2": (4, 2), "head": (8, 2)}[kind]
-            while ntiles % nt:
-                nt //= 2
-            while self.MTs % mt:
-                mt //= 2
-            if kind == "w13":
-                nt = max(nt, 2)
-            return mt, nt, (4 if kch <= 128 else 8)
-        if self.MTs >= 16 and bf16 and self.fuse_norm and kch // 4 >= 12 and (kind == "w2" or (kind == "wo" and ntiles >= 96)) \
-                and ntiles % 2 == 0:
-            # RES GEMMs of the fused-norm models at 256 rows: 4 waves x >= 12 chunks run the steady-state ring kernel (counted waits);
-            # measured: GPT-L w2 (2, 2, 4) 6.16 us against (4, 1, 8) 7.35 / (2, 2, 8) 6.90; GPT-XXL w2 13.2 / 17.1, wo 5.6 / 8.1
-            # (GPT-L's wo, 8 chunks per wave at kw 4, stays (4, 1, 8): 4.64 us)
-            return 2, 2, 4
-        epi = {"qkv": L.EPI_QKV, "wo": L.EPI_RES, "w2": L.EPI_RES, "w13": L.EPI_SWIGLU, "head": L.EPI_ROWS}[kind]
-        fused = self.fuse_norm and kind in ("qkv", "w13", "head")
-        if fused and kch % 8 == 0 and 3 <= kch // 8 <= 6:
-            # normpre kernel (persistent along N since round 3): every workgroup normalises its own rows of the panel once and
-            # walks `_passes` n-groups, so few rows per workgroup and 4 n-tiles per group.  Measured best (tools/gemm_sweep.py,
-            # GPT-L, profiles/r03_gemm_sweep.log): qkv (1, 4, 8) at every chain width (64 / 128 / 256 rows: 6.3 / 8.0 / 9.9 us with
-            # 1 / 2 / 3 passes), w1||w3 and lm_head (2, 4, 8) (8.5 / 10.7 / 12.6 us and 11.1 / 14.8 / 22.0 us)
-            mt = 1 if kind == "qkv" else max(1, self.mt // 2)
-            nt = 4
-            while ntiles % nt or (kind == "w13" and nt & 1 and nt > 1):
-                nt //= 2
-            return mt, max(nt, 2 if kind == "w13" else 1), 8
-        nt = 4 if ntiles >= 1024 else (2 if (kind == "w13" or ntiles >= 352) else 1)
-        while ntiles % nt:
-            nt //= 2
-        mt = self.mt
-        while mt > 1 and (ntiles // nt) * (self.MTs // mt) < 160 and self.MTs % (mt // 2) == 0:
-            mt //= 2
-        kmax = self.lib.lgen_gemm_max_kw(epi, 1 if fused else 0, mt, nt)
-        kw = max(1, min(kmax, 16 if kch >= 64 else 8, kch // 2))
-        return mt, nt, kw
-
-    def _tile_shape(self, kind: str):
-        """(wm, wn, mtv, ntv, kb, stages, lw) of the big-M tile family (csrc/gemm_tile.hip) for one decode GEMM, or None where the
-        skinny kernels stay: chains of >= 256 rows, bf16, RMSNorm fused (the family's norm consumers read the producer's statistics),
-        one position for all rows.  Measured on MI355X, GPT-L, 256 rows (tools/gemm_tile_sweep.py, us per launch, skinny -> tile):
-        wqkv 10.2 -> 9.8, wo 4.85 -> 4.1, w1||w3 13.1 -> 10.6, w2 7.8 -> 7.7, lm_head 23.2 -> 20.9."""
-        if kind in self._tile_refused:
-            return None
-        if kind in self.tile_shape_override:
-            return self.tile_shape_override[kind]
-        if not self.use_tile or self.MTs < 16 or self.dtype != torch.bfloat16 or not self.fuse_norm:
-            return None
-        if kind == "qkv" and (self.pos_rows is not None or self.hd < 16):
-            return None
-        if (self.d, self.F, self.V) != TABLE_MODEL and self.tile_autotune:
-            tuned = self._tuned_shapes()
-            if tuned is not None:
-                return tuned[kind]
-        table = MODEL_TILE_SCHEDULES.get((self.d, self.F, self.V), TILE_SCHEDULES)   # unknown widths: GPT-L's shapes by chain width
-        key = tile_schedule_key(self.MTs, table)
-        return None if key is None else table[key][kind]
-
-    # ---- on-device shape search (models / chain widths without a measured table) ---------------------------------------------
-    def _tile_call(self, kind, w, i, s, x_in, nw):
-        """One launch of the tile family for GEMM `kind` of layer i with workgroup shape s; returns the library's status."""
-        lib, st, dt, M, mts = self.lib, L.stream(), self.dt, self.B2, self.MTs
-        d, F, H, hd, hdp, S8 = self.d, self.F, self.H, self.hd, self.hdp, self.S8
-        if kind == "qkv":
-            return lib.lgen_gemm_qkv_rope_tile(L.ptr(w["wqkv"]), L.ptr(x_in), L.ptr(self.qbuf), L.ptr(self.k_cache[i]),
-                                               L.ptr(self.v_cache[i]), L.ptr(self.freqs_cis), self.state.data_ptr(), M, mts, d, H, hd,
-                                               hdp, S8, self.kvs, dt, *s, L.ptr(nw), L.ptr(self.ssq), self.ssq_parts, self.eps, st)
-        wp, xp, out, N, K, epi, ssq_out = {
-            "wo": (w and w["wo"], self.ap, self.hp, d, d, L.EPI_RES, self.ssq),
-            "w13": (w and w["w13"], x_in, self.gp, 2 * F, d, L.EPI_SWIGLU, None),
-            "w2": (w and w["w2"], self.gp, self.hp, d, F, L.EPI_RES, self.ssq),
-            "head": (self.out_w, x_in, self.logits, self.V, d, L.EPI_ROWS, None)}[kind]
-        return lib.lgen_gemm_tile(L.ptr(wp), L.ptr(xp), L.ptr(out), M, mts, N, K, epi, dt, *s, L.ptr(nw),
-                                  L.ptr(self.ssq) if nw is not None else 0, self.ssq_parts, self.eps, L.ptr(ssq_out), st)
-
-    def _tuned_shapes(self):
-        """{kind: shape | None (skinny kernels)} for this model width and chain width, measured once per process on the device."""
-        key = (self.dev.index, self.d, self.F, self.V, self.H, self.MTs, self.pos_rows is not None)
-        if key not in _TUNED:
-            if torch.cuda.is_current_stream_capturing():
-                return None          # (never the first use: prefill and the first decode step run eagerly)
-            _TUNED[key] = self._search_tile_shapes()
-        return _TUNED[key]
-
-    def _search_tile_shapes(self):
-        """Opt-in (LGEN_TILE_AUTOTUNE=1): times every instantiated workgroup shape of the tile family for each decode GEMM as a
-        captured pass over ALL layers' weights (nothing stays cache-resident from one launch to the next, as in the decode chain)
-        and keeps the fastest TILE shape; the skinny kernel is timed for the report only and is chosen only where the library takes
-        no tile shape at all -- the family never depends on a timing (tile and skinny differ in accumulation order).  Runs on the
-        engine's own workspaces, which it saves and restores; a few hundred launches, once per process per (model width, chain
-        width).  The result only changes speed: every tile shape gives the same bits."""
-        keep = {n: getattr(self, n).clone() for n in ("hp", "ap", "gp", "qbuf", "ssq", "logits", "state")}
-        pos = int(self.state[0])
-        kv_keep = (self.k_cache[:, :, :, pos].clone(), self.v_cache[:, :, :, pos].clone())
-        parts_keep = self.ssq_parts
-        self.ssq_parts = self.d // 16
-        self.hp.normal_(0, 1)
-        self.ap.zero_()        # wo / w2 add their product to hp in place: a zero operand keeps the repeated passes finite
-        self.gp.zero_()
-        self.ssq.fill_(16.0)
-        cur = torch.cuda.current_stream()
-        side = torch.cuda.Stream()
-
-        def timed(fn):
-            """ms of one captured pass of fn (min of 2 replays after one warm replay), or None when fn reports a failure"""
-            ok = fn()            # eager: loads the code object, reports unsupported shapes before anything is captured
-            if not ok:
-                return None
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                g = torch.cuda.CUDAGraph()
-                g.capture_begin()
-                fn()
-                g.capture_end()
-                g.replay()
-                best = float("inf")
-                for _ in range(2):
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    g.replay()
-                    e1.record()
-                    e1.synchronize()
-                    best = min(best, e0.elapsed_time(e1))
-            cur.wait_stream(side)
-            return best
-
-        head_w = [None] * 4
-        nlay = self.layers[:min(len(self.layers), 24)]
-        plan = {"qkv": (nlay, "an", TILE_SHAPES_NORM), "w13": (nlay, "fn", TILE_SHAPES_NORM), "head": (head_w, None, TILE_SHAPES_NORM),
-                "wo": (nlay, None, TILE_SHAPES_PLAIN), "w2": (nlay, None, TILE_SHAPES_PLAIN)}
-        out, report = {}, {}
-        saved_override, saved_auto = self.tile_shape_override, self.tile_autotune
-        self.tile_autotune = False
-        try:
-            for kind, (ws, nkey, shapes) in plan.items():
-                if kind == "qkv" and self.pos_rows is not None:
-                    # continuous batching: wqkv stays on the per-row-position skinny kernel (_tile_shape); timing it here would
-                    # append K/V rows at every request's own position, which the save / restore around the search does not cover
-                    out[kind] = None
-                    continue
-
-                def nw_of(w):
-                    return self.norm_w if kind == "head" else (w[nkey] if nkey else None)
-
-                def skinny():
-                    self.tile_shape_override = {k: None for k in ("qkv", "wo", "w13", "w2", "head")}   # -> the skinny kernels
-                    try:
-                        for i, w in enumerate(ws):
-                            if kind == "qkv":
-                                self.qkv_gemm(i, w, self.hp, nw_of(w))
-                            else:
-                                self.gemm_kind(kind, w, self.hp, nw_of(w))
-                    finally:
-                        self.tile_shape_override = saved_override
-                    return True
-
-                def tile(s):
-                    def run():
-                        for i, w in enumerate(ws):
-                            if self._tile_call(kind, w, i, s, self.hp, nw_of(w)) != 0:
-                                return False
-                        return True
-                    return run
-
-                best_t, best_s = float("inf"), None
-                report[kind] = {"skinny": timed(skinny)}
-                for s in shapes:
-                    if self.MTs % (s[0] * s[2]) or (kind == "w13" and s[3] % 2):
-                        continue
-                    t = timed(tile(s))
-                    if t is None:
-                        continue
-                    report[kind][s] = t
-                    if t < best_t:
-                        best_t, best_s = t, s
-                out[kind] = best_s
-        finally:
-            self.tile_shape_override, self.tile_autotune = saved_override, saved_auto
-            torch.cuda.current_stream().synchronize()
-            for n, t in keep.items():
-                getattr(self, n).copy_(t)
-            self.k_cache[:, :, :, pos].copy_(kv_keep[0])
-            self.v_cache[:, :, :, pos].copy_(kv_keep[1])
-            self.ssq_parts = parts_keep
-        self.tile_search_report = report
-        return out
+        """(mt, nt, kw) of the skinny kernel for GEMM `kind` (N, K follow from the kind)."""
+        return self.plan[kind].tiles
 
     def _passes(self, kind: str, N: int, tiles):
-        """(passes, double_buffer) of a fused-norm GEMM: n-groups one workgroup walks with its normalised rows kept in registers
-        (gemm_normpre.hip).  One workgroup of these kernels fills a CU, so the (n-group, m-group) units are dealt out as
-        ~one workgroup per CU: ceil(units / 256) passes each."""
-        if kind in self.pass_override:
-            return self.pass_override[kind]
-        if not (self.fuse_norm and kind in ("qkv", "w13", "head")):
-            return 1, 0
-        mt, nt, _ = tiles
-        units = (N // 16 // nt) * (self.MTs // max(1, math.gcd(self.MTs, mt)))
-        passes = min(64, max(1, -(-units // 256)))   # (the library takes 1..64: a scheduling choice only, results are identical)
-        # weights of the next n-group in a second register set: no faster than reloading after the MFMAs (10.74 vs 10.76 us,
-        # w1||w3 at 128 rows) and bimodal inside the decode graph (73 / 63 img/s, tools/exp_r3c.py): off
-        return passes, 0
+        return S.skinny_passes(self.plan.inputs, self.fuse_norm, kind, tiles)
+
+    def gemm_schedule(self) -> dict:
+        return S.gemm_schedule(self.plan)
+
+    def tile_schedule_source(self) -> str:
+        return S.tile_schedule_source(self.plan)
+
+    def tile_schedule_tested(self) -> bool:
+        return S.tile_schedule_tested(self.plan)
+
+    def launches_per_step(self) -> int:
+        return S.launches_per_step(self.plan)
 
     # ---- launches -----------------------------------------------------------------------------
-    def _grouped_stats(self):
+    def _tile_stats(self, g: S.GemmPlan):
         """(statistics buffer, partials per row) for a fused-norm consumer of the TILE family: the producer's rows as they are where
-        the consumers' fast path takes them, else their 4 lane-group sums, computed here by one small launch (bit-identical)."""
-        parts = self.ssq_parts
-        fast_path = parts % 16 == 0 and parts <= 128       # the consumers stage such rows in LDS and sum contiguous quarters
-        if fast_path or parts % 4 or parts <= 4:           # (parts % 4: lgen_ssq_group4 does not take the row; the consumer refuses it too)
-            return self.ssq, parts
-        L.check(self.lib.lgen_ssq_group4(L.ptr(self.ssq), L.ptr(self.ssq_g), self.MTs * 16, parts, L.stream()), "ssq_group4")
+        the consumers' fast path takes them, else (`g.group_stats`) their 4 lane-group sums, computed here by one small launch
+        (bit-identical)."""
+        if not g.group_stats:
+            return self.ssq, self.ssq_parts
+        L.check(self.lib.lgen_ssq_group4(L.ptr(self.ssq), L.ptr(self.ssq_g), self.MTs * 16, self.ssq_parts, L.stream()), "ssq_group4")
         return self.ssq_g, 4
 
-    def gemm(self, wp, xp, out, M, mts, N, K, epi, tiles, norm_w=None, ssq_out=None, sched=None, tile=None, kind=None):
-        if tile is not None:
-            sq, parts = self._grouped_stats() if norm_w is not None else (None, self.ssq_parts)
-            rc = self.lib.lgen_gemm_tile(L.ptr(wp), L.ptr(xp), L.ptr(out), M, mts, N, K, epi, self.dt, *tile, L.ptr(norm_w),
-                                         L.ptr(sq), parts, self.eps, L.ptr(ssq_out), L.stream())
-            if rc != L.ERR_UNSUPPORTED:   # no instantiation / shape does not divide: the skinny kernel below
-                L.check(rc, "lgen_gemm_tile")
-                return
-            if kind is not None:          # ... from now on, and gemm_schedule() / tile_schedule_tested() say so (ADVICE r5)
-                self._tile_refused.add(kind)
-                self._graphs = {}
+    def _refuse_tile(self, kind) -> S.GemmPlan:
+        """The library took no instantiation of `kind`'s tile shape (ERR_UNSUPPORTED): the skinny kernel from now on, and
+        gemm_schedule() / tile_schedule_tested() say so."""
+        self._tile_refused.add(kind)
+        self._graphs = {}
+        return self.plan[kind]
+
+    def _norm_input(self, nw):
+        """(input, norm weight) of a norm consumer on the decode workspace: fused -> the residual stream and the weight for the
+        GEMM's prologue, else lgen_rmsnorm into `xnp` now and no weight."""
+        if self.fuse_norm:
+            return self.hp, nw
+        L.check(self.lib.lgen_rmsnorm(L.ptr(self.hp), L.ptr(nw), L.ptr(self.xnp), self.MTs, self.d, self.eps, self.dt, L.stream()),
+                "rmsnorm")
+        return self.xnp, None
+
+    def gemm(self, wp, xp, out, M, mts, N, K, epi, tiles, norm_w=None, ssq_out=None, sched=None):
+        """One launch of the skinny GEMM kernels."""
         mt, nt, kw = tiles
         if mts % mt:
             mt = math.gcd(mts, mt)
@@ -650,113 +331,71 @@ class DecodeEngine:
                                    L.ptr(ssq_out), passes, L.stream()), "lgen_gemm")
 
     def qkv_gemm(self, i, w, x_in, nw):
-        """[attention_norm +] wqkv + RoPE + KV append of layer i (gpt.py:214-226): the big-M tile form where it applies, else the
-        skinny kernels (per-row positions, narrow chains, other storage types)."""
+        """[attention_norm +] wqkv + RoPE + KV append of layer i (gpt.py:214-226): the big-M tile form where the plan says so, else
+        the skinny kernels (per-row positions, narrow chains, other storage types)."""
         lib, st, dt, M, mts = self.lib, L.stream(), self.dt, self.B2, self.MTs
         d, H, hd, hdp, S8 = self.d, self.H, self.hd, self.hdp, self.S8
         rows = self.pos_rows is not None
         pos_ptr = self.pos_rows.data_ptr() if rows else self.state.data_ptr()
-        ssq = self.ssq if nw is not None else None
-        bq = self._tile_shape("qkv")
-        if bq is not None and nw is not None and not rows:
-            sq, parts = self._grouped_stats()
+        g = self.plan["qkv"]
+        if g.shape is not None and nw is not None:
+            sq, parts = self._tile_stats(g)
             rc = lib.lgen_gemm_qkv_rope_tile(L.ptr(w["wqkv"]), L.ptr(x_in), L.ptr(self.qbuf), L.ptr(self.k_cache[i]),
                                              L.ptr(self.v_cache[i]), L.ptr(self.freqs_cis), pos_ptr, M, mts, d, H, hd, hdp, S8,
-                                             self.kvs, dt, *bq, L.ptr(nw), L.ptr(sq), parts, self.eps, st)
+                                             self.kvs, dt, *g.shape, L.ptr(nw), L.ptr(sq), parts, self.eps, st)
             if rc != L.ERR_UNSUPPORTED:
                 L.check(rc, "gemm_qkv_rope_tile")
                 return
-            self._tile_refused.add("qkv")
-            self._graphs = {}
-        tq = self._tiles("qkv", 3 * d, d)
-        sq = self._passes("qkv", 3 * d, tq)
+            g = self._refuse_tile("qkv")
         qkv_fn = lib.lgen_gemm_qkv_rope_rows if rows else lib.lgen_gemm_qkv_rope
         L.check(qkv_fn(L.ptr(w["wqkv"]), L.ptr(x_in), L.ptr(self.qbuf), L.ptr(self.k_cache[i]), L.ptr(self.v_cache[i]),
-                       L.ptr(self.freqs_cis), pos_ptr, M, mts, d, H, hd, hdp, S8, self.kvs, dt, tq[0], tq[1], tq[2], L.ptr(nw),
-                       L.ptr(ssq), self.ssq_parts, self.eps, sq[0] if nw is not None else 1, st), "gemm_qkv_rope")
+                       L.ptr(self.freqs_cis), pos_ptr, M, mts, d, H, hd, hdp, S8, self.kvs, dt, *g.tiles, L.ptr(nw),
+                       L.ptr(self.ssq if nw is not None else None), self.ssq_parts, self.eps, g.passes[0] if nw is not None else 1, st),
+                "gemm_qkv_rope")
 
-    def gemm_kind(self, kind, w, x_in=None, nw=None):
+    def gemm_kind(self, kind, w, x_in=None, nw=None, tile=True):
         """One decode GEMM of `kind` ("wo" | "w13" | "w2" | "head") on the decode workspaces with the shapes the decode graph uses
-        (also what bench.py's roofline leg and the sweep tools time)."""
+        (also what bench.py's roofline leg and the sweep tools time).  tile=False: the skinny kernel whatever the plan says."""
         d, F, M, mts = self.d, self.F, self.B2, self.MTs
-        fuse = self.fuse_norm
-        ssq = self.ssq if fuse else None
+        ssq = self.ssq if self.fuse_norm else None
+        if x_in is None:
+            x_in = self.hp
         if kind == "wo":
-            self.gemm(w["wo"], self.ap, self.hp, M, mts, d, d, L.EPI_RES, self._tiles("wo", d, d), ssq_out=ssq, tile=self._tile_shape("wo"), kind="wo")
+            wp, xp, out, epi, ssq_out = w["wo"], self.ap, self.hp, L.EPI_RES, ssq
         elif kind == "w13":
-            t13 = self._tiles("w13", 2 * F, d)
-            self.gemm(w["w13"], x_in if x_in is not None else self.hp, self.gp, M, mts, 2 * F, d, L.EPI_SWIGLU, t13, norm_w=nw,
-                      sched=self._passes("w13", 2 * F, t13), tile=self._tile_shape("w13") if nw is not None else None, kind="w13")
+            wp, xp, out, epi, ssq_out = w["w13"], x_in, self.gp, L.EPI_SWIGLU, None
         elif kind == "w2":
-            self.gemm(w["w2"], self.gp, self.hp, M, mts, d, F, L.EPI_RES, self._tiles("w2", d, F), ssq_out=ssq, tile=self._tile_shape("w2"), kind="w2")
+            wp, xp, out, epi, ssq_out = w["w2"], self.gp, self.hp, L.EPI_RES, ssq
         elif kind == "head":
-            th = self._tiles("head", self.V, d)
-            self.gemm(self.out_w, x_in if x_in is not None else self.hp, self.logits, M, mts, self.V, d, L.EPI_ROWS, th, norm_w=nw,
-                      sched=self._passes("head", self.V, th), tile=self._tile_shape("head") if nw is not None else None, kind="head")
+            wp, xp, out, epi, ssq_out = self.out_w, x_in, self.logits, L.EPI_ROWS, None
         else:
             raise ValueError(kind)
-
-    def tile_schedule_source(self) -> str:
-        """Where the tile shapes of gemm_schedule() come from: "override" (LGEN_TILE_SHAPES), "table" (MODEL_TILE_SCHEDULES: measured
-        and pinned per registry model), "table (GPT-L shapes by chain width)" (other widths), "search" (LGEN_TILE_AUTOTUNE=1: timed on
-        this device at first use), or "none" (chains below 256 rows / other storage types)."""
-        if self.tile_shape_override:
-            return "override"
-        if not self.use_tile or self.MTs < 16 or self.dtype != torch.bfloat16 or not self.fuse_norm:
-            return "none"
-        if (self.d, self.F, self.V) != TABLE_MODEL and self.tile_autotune:
-            return "search"
-        return "table" if (self.d, self.F, self.V) in MODEL_TILE_SCHEDULES else "table (GPT-L shapes by chain width)"
-
-    def tile_schedule_tested(self) -> bool:
-        """True when every GEMM of the decode graph runs a schedule an end-to-end oracle test names (tests/test_gpu_headline.py):
-        the skinny kernels (chains below 256 rows: the round-2/3 tests of every config) or a tested key of this model's tile table."""
-        sched = self.gemm_schedule()
-        if all(v["family"] == "skinny" for v in sched.values()):
-            return not self.tile_shape_override and not self.tile_override and not self.pass_override
-        model = (self.d, self.F, self.V)
-        table = MODEL_TILE_SCHEDULES.get(model)
-        if table is None or self.tile_schedule_source() != "table":
-            return False
-        names = {"wqkv": "qkv", "wo": "wo", "w13": "w13", "w2": "w2", "lm_head": "head"}
-        run = {k: tuple(v.get("shape(wm,wn,mtv,ntv,kb,stages,lw)", ())) for k, v in sched.items()}
-        return any(all(run[k] == table[m][names[k]] for k in run) for m in TESTED_MODEL_SCHEDULES.get(model, ()))
-
-    def gemm_schedule(self) -> dict:
-        """The kernel family and shapes the decode graph launches per GEMM kind (bench.py prints it; tests pin it)."""
-        d, F = self.d, self.F
-        dims = {"wqkv": ("qkv", 3 * d, d), "wo": ("wo", d, d), "w13": ("w13", 2 * F, d), "w2": ("w2", d, F), "lm_head": ("head", self.V, d)}
-        out = {}
-        for name, (kind, N, K) in dims.items():
-            ts = self._tile_shape(kind)
-            if ts is not None and (self.fuse_norm or kind in ("wo", "w2")):
-                out[name] = {"family": "tile", "shape(wm,wn,mtv,ntv,kb,stages,lw)": list(ts)}
-            else:
-                t = self._tiles(kind, N, K)
-                out[name] = {"family": "skinny", "tile(mt,nt,kw)": list(t), "passes": self._passes(kind, N, t)[0]}
-        return out
+        N, K = self.plan.inputs.dims(kind)
+        g = self.plan[kind]
+        if tile and g.shape is not None and (nw is not None or kind in ("wo", "w2")):
+            sq, parts = self._tile_stats(g) if nw is not None else (None, self.ssq_parts)
+            rc = self.lib.lgen_gemm_tile(L.ptr(wp), L.ptr(xp), L.ptr(out), M, mts, N, K, epi, self.dt, *g.shape, L.ptr(nw),
+                                         L.ptr(sq), parts, self.eps, L.ptr(ssq_out), L.stream())
+            if rc != L.ERR_UNSUPPORTED:
+                L.check(rc, "lgen_gemm_tile")
+                return
+            g = self._refuse_tile(kind)
+        self.gemm(wp, xp, out, M, mts, N, K, epi, g.tiles, norm_w=nw, ssq_out=ssq_out, sched=g.passes)
 
     def _layers_and_logits(self, want_logits: bool = True):
         """L x [attention_norm+wqkv+rope+append | attention | wo+res | ffn_norm+w1,w3+swiglu | w2+res], then
         norm+output: 5 launches per layer (RMSNorm rides in the GEMM prologues, its statistics in the
         epilogues of the GEMMs that produce the residual stream)."""
         lib, st, dt, M, mts = self.lib, L.stream(), self.dt, self.B2, self.MTs
-        d, F, H, hd, hdp, S8 = self.d, self.F, self.H, self.hd, self.hdp, self.S8
+        H, hd, hdp, S8 = self.H, self.hd, self.hdp, self.S8
         # one device scalar (generate(): all rows at the same position) or one position per row (serve.py)
         rows = self.pos_rows is not None
         pos_ptr = self.pos_rows.data_ptr() if rows else self.state.data_ptr()
         attn_fn = lib.lgen_attn_decode_rows if rows else lib.lgen_attn_decode
-        fuse = self.fuse_norm
         pm = self._mask()
 
-        nlayers = len(self.layers)
         for i, w in enumerate(self.layers):
-            if fuse:
-                x_in, nw = self.hp, w["an"]
-            else:
-                L.check(lib.lgen_rmsnorm(L.ptr(self.hp), L.ptr(w["an"]), L.ptr(self.xnp), mts, d, self.eps, dt, st), "rmsnorm")
-                x_in, nw = self.xnp, None
-            self.qkv_gemm(i, w, x_in, nw)
+            self.qkv_gemm(i, w, *self._norm_input(w["an"]))
             if self._prof is not None:  # bench.py roofline leg: HIP events on the launch stream
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
@@ -767,29 +406,11 @@ class DecodeEngine:
                 e1.record()
                 self._prof["events"].append((e0, e1))
             self.gemm_kind("wo", w)
-            self.ssq_parts = d // 16
-            if fuse:
-                x_in, nw = self.hp, w["fn"]
-            else:
-                L.check(lib.lgen_rmsnorm(L.ptr(self.hp), L.ptr(w["fn"]), L.ptr(self.xnp), mts, d, self.eps, dt, st), "rmsnorm")
-                x_in, nw = self.xnp, None
-            self.gemm_kind("w13", w, x_in, nw)
+            self.ssq_parts = self.d // 16
+            self.gemm_kind("w13", w, *self._norm_input(w["fn"]))
             self.gemm_kind("w2", w)
         if want_logits:
-            if fuse:
-                x_in, nw = self.hp, self.norm_w
-            else:
-                L.check(lib.lgen_rmsnorm(L.ptr(self.hp), L.ptr(self.norm_w), L.ptr(self.xnp), mts, d, self.eps, dt, st), "rmsnorm")
-                x_in, nw = self.xnp, None  # the next decode step starts there
-            self.gemm_kind("head", None, x_in, nw)
-
-    def launches_per_step(self) -> int:
-        """Kernel launches of one captured decode step (embed + L layers + norm/lm_head + sampler)."""
-        per_layer = 5 if self.fuse_norm else 7
-        parts = self.d // 16
-        grouped = self.fuse_norm and self._tile_shape("w13") is not None and not ((parts % 16 == 0 and parts <= 128) or parts % 4 or parts <= 4)
-        extra = 2 * len(self.layers) + 1 if grouped else 0   # lgen_ssq_group4 in front of wqkv, w1||w3 and lm_head (GPT-3B)
-        return 1 + len(self.layers) * per_layer + (1 if self.fuse_norm else 2) + 1 + extra
+            self.gemm_kind("head", None, *self._norm_input(self.norm_w))   # (not fused: xnp is also where the next decode step starts)
 
     def _mask(self):
         if self._force_causal:
@@ -830,8 +451,7 @@ class DecodeEngine:
         """cond [B2, T, caption_dim] -> [B2, T, d] through the HIP GEMMs (fc1+gelu_tanh, fc2)."""
         B2, T, C = cond.shape
         x = cond.reshape(B2 * T, C).to(self.dtype)
-        mts = _ceil_div(B2 * T, 16)
-        mts = _ceil_div(mts, 8) * 8 if mts > 4 else (4 if mts == 3 else mts)
+        mts = S.round_mts(B2 * T)
         xp = pack_act(x, mts)
         hid = torch.zeros(self.cap_hidden // self.kc, mts, 64, self.epl, dtype=self.dtype, device=self.dev)
         out = torch.zeros(mts * 16, self.d, dtype=self.dtype, device=self.dev)
@@ -853,8 +473,7 @@ class DecodeEngine:
         if B2 != self.B2 or T > S8:
             raise ValueError(f"sequence forward of [{B2}, {T}] rows on caches set up for [{self.B2}, {S8}]")
         R = B2 * T
-        mts = _ceil_div(R, 16)
-        mts = _ceil_div(mts, 8) * 8 if mts > 4 else (4 if mts == 3 else mts)
+        mts = S.round_mts(R)
         key = (R, mts)
         ws = getattr(self, "_pf_ws", None)
         if ws is None or ws["key"] != key:
@@ -914,15 +533,9 @@ class DecodeEngine:
         return lg[:R].view(S, B2, self.V).transpose(0, 1).float().contiguous()
 
     def _final_logits(self):
-        """norm + output on the decode workspace (gpt.py:367-368)."""
-        lib, st, dt, M, mts, d = self.lib, L.stream(), self.dt, self.B2, self.MTs, self.d
-        th = self._tiles("head", self.V, d)
-        if self.fuse_norm:
-            x_in, nw = self.hp, self.norm_w
-        else:
-            L.check(lib.lgen_rmsnorm(L.ptr(self.hp), L.ptr(self.norm_w), L.ptr(self.xnp), mts, d, self.eps, dt, st), "rmsnorm")
-            x_in, nw = self.xnp, None
-        self.gemm(self.out_w, x_in, self.logits, M, mts, self.V, d, L.EPI_ROWS, th, norm_w=nw, sched=self._passes("head", self.V, th))
+        """norm + output on the decode workspace (gpt.py:367-368) after the t2i prefill: on the SKINNY kernels at every chain width
+        (tile and skinny differ in accumulation order; this is the form the t2i oracle tests hold)."""
+        self.gemm_kind("head", None, *self._norm_input(self.norm_w), tile=False)
 
     # ---- Exp(1) noise: what torch.multinomial draws, one [B, V] fp32 exponential_ per sampled token ----
     def _noise_buffer(self, N, B):

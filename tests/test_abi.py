@@ -100,13 +100,17 @@ def test_save_codes_format(tmp_path):
     assert f.dtype == np.int64 and f.shape == (1, 2, 9) and np.array_equal(f[:, 1], codes.numpy()[:, 1]) and y.tolist() == [7]
 
 
+def _schedule_inputs(lib, d, F, mts, dtype=torch.bfloat16, V=16384, head_dim=64, n_layer=1, **kw):
+    from llamagen_amd.gemm_schedule import ScheduleInputs
+    return ScheduleInputs(d=d, F=F, V=V, head_dim=head_dim, n_layer=n_layer, MTs=mts, dtype=dtype, max_kw=lib.lgen_gemm_max_kw, **kw)
+
+
 def test_tile_heuristics_are_valid_for_every_registry_model(lib):
-    """engine._tiles must hand the library a tile shape it accepts for every GPT registry size and batch
+    """gemm_schedule.skinny_tiles must hand the library a tile shape it accepts for every GPT registry size and batch
     (argument validation runs before the launch; without a GPU the launch itself then fails with a hip error,
     which is fine here -- LGEN_ERR_BAD_ARG / UNSUPPORTED is not)."""
-    import types
     from llamagen_amd import _lib as L
-    from llamagen_amd.engine import DecodeEngine, _ceil_div
+    from llamagen_amd import gemm_schedule as S
     from llamagen_amd.gpt import find_multiple
     from oracle.llamagen_oracle import GPT_SIZES
     bad = []
@@ -115,18 +119,18 @@ def test_tile_heuristics_are_valid_for_every_registry_model(lib):
         F = find_multiple(int(2 * (4 * d) / 3), 256)
         for dtype, kc in ((L.BF16, 32), (L.F32, 16)):
             for B2 in (1, 2, 6, 32, 64, 128, 256):
-                mts = _ceil_div(B2, 16)
-                mts = _ceil_div(mts, 8) * 8 if mts > 8 else (8 if mts > 4 else (4 if mts == 3 else mts))
+                mts = S.round_mts(B2)
                 kch = d // kc
                 for fuse in (False, True):
                     fuse = fuse and dtype == L.BF16 and kch % 8 == 0 and 3 <= kch // 8 <= 6
-                    eng = types.SimpleNamespace(tile_override={}, pass_override={}, fuse_norm=fuse, mt=min(mts, 4), MTs=mts, kc=kc,
-                                                lib=lib, dtype=torch.bfloat16 if dtype == L.BF16 else torch.float32)
+                    plan = S.make_plan(_schedule_inputs(lib, d, F, mts, torch.bfloat16 if dtype == L.BF16 else torch.float32,
+                                                        head_dim=d // H), fuse)
                     for kind, N, K, epi in (("qkv", 3 * d, d, None), ("wo", d, d, L.EPI_RES), ("w13", 2 * F, d, L.EPI_SWIGLU),
                                             ("w2", d, F, L.EPI_RES), ("head", 16384, d, L.EPI_ROWS)):
-                        mt, nt, kw = DecodeEngine._tiles(eng, kind, N, K)
+                        assert plan.inputs.dims(kind) == (N, K)
+                        mt, nt, kw = plan[kind].tiles
                         nw = 8 if (fuse and kind in ("qkv", "w13", "head")) else 0
-                        passes, _ = DecodeEngine._passes(eng, kind, N, (mt, nt, kw))   # n-groups per workgroup (explicit argument, ABI v7)
+                        passes, _ = plan[kind].passes   # n-groups per workgroup (explicit argument, ABI v7)
                         assert 1 <= passes <= 64 and (passes == 1 or nw), (kind, passes)
                         if kind == "qkv":
                             rc = lib.lgen_gemm_qkv_rope(8, 8, 8, 8, 8, 8, 8, B2, mts, d, H, d // H, 64 if d // H <= 64 else 128, 584, 0,
@@ -139,16 +143,12 @@ def test_tile_heuristics_are_valid_for_every_registry_model(lib):
 
 
 def test_measured_tile_tables_of_round_3(lib):
-    """The shapes the round-3 sweeps measured best (profiles/r03_wide_sweep.log) are the ones engine._tiles hands out: wide models
+    """The shapes the round-3 sweeps measured best (profiles/r03_wide_sweep.log) are the ones gemm_schedule.skinny_tiles hands out: wide models
     (GPT-3B: not fused, >= 96 k-chunks) at 128 / 256 rows, and the 4-wave RES GEMMs of the fused-norm models at 256 rows."""
-    import types
-    from llamagen_amd.engine import DecodeEngine
+    from llamagen_amd import gemm_schedule as S
 
     def tiles(d, F, mts, fuse):
-        eng = types.SimpleNamespace(tile_override={}, pass_override={}, fuse_norm=fuse, mt=min(mts, 4), MTs=mts, kc=32, lib=lib,
-                                    dtype=torch.bfloat16)
-        return {k: DecodeEngine._tiles(eng, k, n, kk) for k, n, kk in (("qkv", 3 * d, d), ("wo", d, d), ("w13", 2 * F, d),
-                                                                      ("w2", d, F), ("head", 16384, d))}
+        return {k: S.skinny_tiles(_schedule_inputs(lib, d, F, mts), fuse, k) for k in S.KINDS}
     assert tiles(3200, 8704, 16, False) == {"qkv": (4, 4, 4), "wo": (4, 4, 4), "w13": (8, 2, 4), "w2": (4, 4, 8), "head": (8, 2, 4)}
     assert tiles(3200, 8704, 8, False) == {"qkv": (4, 4, 4), "wo": (4, 2, 4), "w13": (4, 4, 4), "w2": (4, 2, 8), "head": (8, 2, 4)}
     small = tiles(3200, 8704, 4, False)                                   # 64 rows: the generic rule, untouched
@@ -161,14 +161,14 @@ def test_measured_tile_tables_of_round_3(lib):
 
 
 def test_pinned_tile_schedules_are_shapes_the_library_takes(lib):
-    """Round 5: engine.MODEL_TILE_SCHEDULES replaces the on-device search.  Every shape of every table must be one the library
+    """Round 5: gemm_schedule.MODEL_TILE_SCHEDULES replaces the on-device search.  Every shape of every table must be one the library
     instantiates for that GEMM at the chain widths the key serves (argument validation runs before the launch: without a GPU the
-    launch then fails with a hip error, which is fine here -- LGEN_ERR_UNSUPPORTED / BAD_ARG is not), the engine must pick the
+    launch then fails with a hip error, which is fine here -- LGEN_ERR_UNSUPPORTED / BAD_ARG is not), the plan must pick the
     model's own table, and tile_schedule_tested() must say "tested" exactly for the keys an end-to-end test names."""
-    import types
     from llamagen_amd import _lib as L
-    from llamagen_amd.engine import (DecodeEngine, MODEL_TILE_SCHEDULES, TESTED_MODEL_SCHEDULES, TILE_SCHEDULES, TILE_SCHEDULE_EXACT,
-                                     tile_schedule_key)
+    from llamagen_amd import gemm_schedule as S
+    from llamagen_amd.gemm_schedule import (MODEL_TILE_SCHEDULES, TESTED_MODEL_SCHEDULES, TILE_SCHEDULES, TILE_SCHEDULE_EXACT,
+                                            tile_schedule_key)
     heads = {1024: 16, 1280: 20, 1536: 24, 3200: 32}
     bad = []
     for (d, F, V), table in MODEL_TILE_SCHEDULES.items():
@@ -192,36 +192,31 @@ def test_pinned_tile_schedules_are_shapes_the_library_takes(lib):
                         bad.append(((d, F, V), key, mts, kind, s, rc))
     assert not bad, bad
 
-    def eng(d, F, V, mts, **kw):
-        e = types.SimpleNamespace(d=d, F=F, V=V, MTs=mts, hd=64, dtype=torch.bfloat16, fuse_norm=True, use_tile=True, tile_autotune=False,
-                                  tile_shape_override={}, tile_override={}, pass_override={}, pos_rows=None, mt=4, kc=32, lib=lib,
-                                  _tile_refused=set())
-        e.__dict__.update(kw)
-        for name in ("_tile_shape", "_tiles", "_passes", "gemm_schedule", "tile_schedule_source", "tile_schedule_tested"):
-            setattr(e, name, types.MethodType(getattr(DecodeEngine, name), e))
-        return e
-    gl = eng(1024, 2816, 16384, 40)
-    assert gl._tile_shape("w13") == TILE_SCHEDULES[40]["w13"] and gl.tile_schedule_source() == "table" and gl.tile_schedule_tested()
-    assert not eng(1024, 2816, 16384, 32).tile_schedule_tested()                    # 512 rows: measured, but no end-to-end oracle test
-    assert eng(1024, 2816, 16384, 24).tile_schedule_tested()                        # 384 rows: the 256-row table
-    assert eng(1024, 2816, 16384, 4).tile_schedule_tested()                         # 64 rows: skinny kernels
-    xxl = eng(1536, 4096, 16384, 24)
-    assert xxl._tile_shape("w2") == MODEL_TILE_SCHEDULES[(1536, 4096, 16384)][16]["w2"] and xxl.tile_schedule_tested()
-    b3 = eng(3200, 8704, 16384, 16)
-    assert b3._tile_shape("qkv") == (8, 1, 1, 6, 2, 4, 4) and b3.tile_schedule_tested()
-    assert eng(1536, 4096, 16384, 32)._tile_shape("qkv") == (4, 1, 2, 6, 2, 4, 4) and eng(1536, 4096, 16384, 32).tile_schedule_tested()   # round 6: 512 rows
-    b3w = eng(3200, 8704, 16384, 32)
-    assert b3w._tile_shape("w2") == (2, 2, 4, 2, 2, 4, 4) and b3w._tile_shape("qkv") == (4, 1, 2, 10, 2, 4, 4) and b3w.tile_schedule_tested()
-    xl = eng(1280, 3584, 16384, 16)                                                 # GPT-XL (config 5): its own table since round 6
-    assert xl._tile_shape("qkv") == (4, 1, 1, 4, 4, 4, 4) and xl.tile_schedule_source() == "table" and xl.tile_schedule_tested()
-    xl384 = eng(1280, 3584, 16384, 24)                                              # 2 x 12 batches of 16: its own key
-    assert xl384._tile_shape("w13") == (4, 1, 2, 8, 2, 4, 4) and xl384.tile_schedule_tested() and eng(1280, 3584, 16384, 20)._tile_shape("w13") == (4, 1, 1, 8, 2, 4, 4)
-    other = eng(768, 2048, 16384, 16)                                               # GPT-B: no table of its own -> GPT-L's shapes by width
-    assert other._tile_shape("wo") == TILE_SCHEDULES[16]["wo"] and not other.tile_schedule_tested()
-    assert other.tile_schedule_source().startswith("table (GPT-L")
-    refused = eng(768, 2048, 16384, 16, _tile_refused={"w2"})                       # a shape the library refused at first launch: reported as skinny
-    assert refused._tile_shape("w2") is None and refused.gemm_schedule()["w2"]["family"] == "skinny"
-    assert not eng(1024, 2816, 16384, 40, tile_shape_override={"wo": (2, 2, 1, 1, 4, 4, 4)}).tile_schedule_tested()
+    def plan(d, F, V, mts, refused=(), **kw):
+        return S.make_plan(_schedule_inputs(lib, d, F, mts, V=V, **kw), True, refused=refused)
+    tested = S.tile_schedule_tested
+    gl = plan(1024, 2816, 16384, 40)
+    assert gl["w13"].shape == TILE_SCHEDULES[40]["w13"] and S.tile_schedule_source(gl) == "table" and tested(gl)
+    assert not tested(plan(1024, 2816, 16384, 32))                                  # 512 rows: measured, but no end-to-end oracle test
+    assert tested(plan(1024, 2816, 16384, 24))                                      # 384 rows: the 256-row table
+    assert tested(plan(1024, 2816, 16384, 4))                                       # 64 rows: skinny kernels
+    xxl = plan(1536, 4096, 16384, 24)
+    assert xxl["w2"].shape == MODEL_TILE_SCHEDULES[(1536, 4096, 16384)][16]["w2"] and tested(xxl)
+    b3 = plan(3200, 8704, 16384, 16)
+    assert b3["qkv"].shape == (8, 1, 1, 6, 2, 4, 4) and tested(b3)
+    assert plan(1536, 4096, 16384, 32)["qkv"].shape == (4, 1, 2, 6, 2, 4, 4) and tested(plan(1536, 4096, 16384, 32))   # round 6: 512 rows
+    b3w = plan(3200, 8704, 16384, 32)
+    assert b3w["w2"].shape == (2, 2, 4, 2, 2, 4, 4) and b3w["qkv"].shape == (4, 1, 2, 10, 2, 4, 4) and tested(b3w)
+    xl = plan(1280, 3584, 16384, 16)                                                # GPT-XL (config 5): its own table since round 6
+    assert xl["qkv"].shape == (4, 1, 1, 4, 4, 4, 4) and S.tile_schedule_source(xl) == "table" and tested(xl)
+    xl384 = plan(1280, 3584, 16384, 24)                                             # 2 x 12 batches of 16: its own key
+    assert xl384["w13"].shape == (4, 1, 2, 8, 2, 4, 4) and tested(xl384) and plan(1280, 3584, 16384, 20)["w13"].shape == (4, 1, 1, 8, 2, 4, 4)
+    other = plan(768, 2048, 16384, 16)                                              # GPT-B: no table of its own -> GPT-L's shapes by width
+    assert other["wo"].shape == TILE_SCHEDULES[16]["wo"] and not tested(other)
+    assert S.tile_schedule_source(other).startswith("table (GPT-L")
+    refused = plan(768, 2048, 16384, 16, refused={"w2"})                            # a shape the library refused at first launch: reported as skinny
+    assert refused["w2"].shape is None and S.gemm_schedule(refused)["w2"]["family"] == "skinny"
+    assert not tested(plan(1024, 2816, 16384, 40, tile_shape_override={"wo": (2, 2, 1, 1, 4, 4, 4)}))
     assert set(TESTED_MODEL_SCHEDULES) == set(MODEL_TILE_SCHEDULES)
     # K/V rows packed tighter than the lane group (round 5): head_dim 100 takes rows of 104 elements (bf16) / 100 (fp32), not 96
     for dtype, stride, want_ok in ((L.BF16, 104, True), (L.BF16, 96, False), (L.BF16, 100, False), (L.F32, 100, True), (L.BF16, 128, True)):
@@ -285,3 +280,45 @@ def test_graft_entry_build_passes():
     version of the library is the one llamagen_amd._lib expects."""
     import __graft_entry__ as g
     g.build()
+
+
+def test_gemm_schedule_reproduces_the_recorded_reports(lib, golden_dir):
+    """tests/golden/gemm_schedule_grid.json holds what DecodeEngine.gemm_schedule() / tile_schedule_source() / tile_schedule_tested() /
+    launches_per_step() answered when the schedule still lived in engine.py methods, for every registry model x storage type x chain
+    width x per-row positions (RMSNorm fused where the engine fuses it by itself): the pure module must answer the same, exactly.
+    Then the counts the old launches_per_step() got wrong, from first principles: it keyed the grouping launches on w1||w3 alone."""
+    import json
+    from llamagen_amd import gemm_schedule as S
+    from llamagen_amd.gpt import find_multiple
+    from oracle.llamagen_oracle import GPT_SIZES
+    assert [S.round_mts(r) for r in (1, 16, 17, 33, 48, 49, 65, 128, 129, 256, 640)] == [1, 1, 2, 4, 4, 4, 8, 8, 16, 16, 40]
+    with open(os.path.join(golden_dir, "gemm_schedule_grid.json")) as f:
+        gold = json.load(f)
+    assert gold["models"] == list(GPT_SIZES)
+    want = iter(gold["index"])
+    for name in gold["models"]:
+        sz = GPT_SIZES[name]
+        d = sz["dim"]
+        F = find_multiple(int(2 * (4 * d) / 3), 256)
+        for dtype in gold["dtypes"]:
+            for mts in gold["mts"]:
+                c = _schedule_inputs(lib, d, F, mts, {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}[dtype],
+                                     head_dim=d // sz["n_head"], n_layer=sz["n_layer"])
+                for rows in gold["per_row_positions"]:
+                    plan = S.make_plan(c, S.fuse_norm_auto(c, rows), rows)
+                    got = {"gemm_schedule": S.gemm_schedule(plan), "schedule_source": S.tile_schedule_source(plan),
+                           "schedule_tested": S.tile_schedule_tested(plan), "launches_per_step": S.launches_per_step(plan)}
+                    assert got == gold["records"][next(want)], (name, dtype, mts, rows)
+    assert next(want, None) is None
+    # GPT-3B, 512 rows: 200 partial sums of squares per row, which the tile consumers' fast path does not take -> every norm consumer
+    # on the tile family gets one lgen_ssq_group4 in front: 24 x (5 + 2) + (1 + 1) + embed + sampler
+    c = _schedule_inputs(lib, 3200, 8704, 32, head_dim=100, n_layer=24)
+    full = S.make_plan(c, True)
+    assert [k for k in S.KINDS if full[k].group_stats] == ["qkv", "w13", "head"] and S.launches_per_step(full) == 24 * 7 + 2 + 2
+    no_w13 = S.make_plan(c, True, refused={"w13"})          # the library refused w1||w3's shape: its 24 grouping launches go, no others
+    assert [k for k in S.KINDS if no_w13[k].group_stats] == ["qkv", "head"] and no_w13["w13"].family == "skinny"
+    assert S.launches_per_step(no_w13) == S.launches_per_step(full) - 24
+    rows = S.make_plan(c, True, per_row_positions=True)      # per-row positions keep wqkv skinny: w1||w3 and lm_head still group
+    assert [k for k in S.KINDS if rows[k].group_stats] == ["w13", "head"] and S.launches_per_step(rows) == S.launches_per_step(full) - 24
+    # GPT-L's rows (64 partials) go through the fast path: nothing is grouped
+    assert not any(S.make_plan(_schedule_inputs(lib, 1024, 2816, 16, n_layer=24), True)[k].group_stats for k in S.KINDS)

@@ -77,8 +77,7 @@ def sweep(m, rows, out):
     }
     best = {}
     for kind, (fn, launches, nbytes) in kinds.items():
-        default = e._tiles({"head": "head"}.get(kind, kind), {"qkv": 3 * d, "wo": d, "w13": 2 * F, "w2": d, "head": V}[kind],
-                           F if kind == "w2" else d)
+        default = e.plan[kind].tiles
         for tl in [default] + [c for c in cands[kind] if c != default]:
             if tl[0] > mts or mts % tl[0]:
                 continue

@@ -126,8 +126,7 @@ def sweep(m, rows, out):
     for kind, (skinny, tile, outs, reset, ws, shapes, Nn, K) in kinds.items():
         if only and kind not in only.split(","):
             continue
-        tl = e._tiles(kind, Nn, K)
-        sc = e._passes(kind, Nn, tl)
+        tl, sc = e.plan[kind].tiles, e.plan[kind].passes
         if kind == "w13":   # the activations of the SwiGLU input are the residual stream
             e.hp.copy_(hp0)
         reset()

@@ -123,7 +123,7 @@ def main():
         vqd()
     torch.cuda.synchronize()
     tA, tG = timed([(A1, s1)]), timed([(G1, s1)])
-    print(f"rows {ROWS} pos {POS}: A alone {tA:8.1f} us   G alone {tG:8.1f} us   (tile {e1._tile_shape('qkv')})", flush=True)
+    print(f"rows {ROWS} pos {POS}: A alone {tA:8.1f} us   G alone {tG:8.1f} us   (tile {e1.plan['qkv'].shape})", flush=True)
     for name, pairs, parts in (("A|G", [(A1, s1), (G2, s2)], (tA, tG)), ("A|A", [(A1, s1), (A2, s2)], (tA, tA)),
                                ("G|G", [(G1, s1), (G2, s2)], (tG, tG))):
         t = timed(pairs)

@@ -25,7 +25,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from llamagen_amd import _lib as L  # noqa: E402
-from llamagen_amd.engine import (TILE_SCHEDULES, pack_act, pack_weight, precompute_freqs_cis_2d)  # noqa: E402
+from llamagen_amd.engine import pack_act, pack_weight, precompute_freqs_cis_2d  # noqa: E402
+from llamagen_amd.gemm_schedule import TILE_SCHEDULES  # noqa: E402
 
 DEV = torch.device("cuda:0")
 DTS = {"bf16": (torch.bfloat16, L.BF16), "fp16": (torch.float16, L.F16), "fp32": (torch.float32, L.F32)}
