@@ -136,8 +136,11 @@ int lgen_gemm_qkv_rope_tile(const void* wp, const void* xp, void* q_out, void* k
  * S8; generate.py only ever clears columns of the T-token prefix, so mask_len = T skips the byte loads for
  * the image tokens).  variant: -1 = the library's choice by shape (one head per 128-thread workgroup below 256 rows; from 256
  * rows the PERSISTENT form: one 4-wave workgroup per CU whose waves walk whole (row, head) items with 16 KiB of K/V loads in
- * flight each -- 64 KB per CU instead of 160, so that the HBM queue stays short for the other chains' kernels), else 0..13
- * (csrc/gpt_ops.hip lists them; every variant computes the same wave-level online softmax). */
+ * flight each -- 64 KB per CU instead of 160, so that the HBM queue stays short for the other chains' kernels), else 0..14
+ * (the ATTN_VARIANTS table of csrc/gpt_ops.hip).  Every variant is an online softmax with one running maximum per wave and
+ * group of keys.  With bf16 / fp16 storage the persistent variants (8..14) compute q . k with packed dot products on the raw
+ * operands and one scale by sf^2 where the workgroup variants (0..7) sum fl(q sf) * fl(k sf): the two forms differ by fp32
+ * round-off (and v_dot2 flushes fp32 accumulator denormals); with fp32 storage all variants use the second form. */
 int lgen_attn_decode(const void* q, const void* k_cache, const void* v_cache, void* out_packed, const int* pos_ptr,
                      const unsigned char* mask, int mask_len, int B2, int MTs, int n_head, int hd, int hdp, int S8,
                      int kv_row_stride, int dtype, int variant, void* stream);

@@ -294,10 +294,7 @@ static int dispatch(const GemmArgs& a, int mt, int nt, int kw, hipStream_t st) {
 
 template <int EPI, bool NORM>
 static int dispatch_dt(const GemmArgs& a, int dtype, int mt, int nt, int kw, hipStream_t st) {
-    if (dtype == LGEN_BF16) return dispatch<BF16, EPI, NORM>(a, mt, nt, kw, st);
-    if (dtype == LGEN_F32) return dispatch<F32, EPI, NORM>(a, mt, nt, kw, st);
-    if (dtype == LGEN_F16) return dispatch<F16, EPI, NORM>(a, mt, nt, kw, st);
-    return LGEN_ERR_BAD_ARG;
+    return lgen_dispatch_dtype(dtype, [&](auto tag) { return dispatch<decltype(tag), EPI, NORM>(a, mt, nt, kw, st); });
 }
 
 // RMSNorm-prologue variants exist for the three consumers of a normalised residual stream
@@ -331,7 +328,7 @@ extern "C" int lgen_gemm_max_kw(int epilogue_kind, int fused_norm, int mt, int n
 extern "C" int lgen_gemm(const void* wp, const void* xp, void* out, int M, int MTs, int N, int K, int epilogue_kind,
                          int dtype, int mt, int nt, int kw, const void* norm_w, const float* ssq_in, int ssq_parts,
                          float eps, float* ssq_out, int passes, void* stream) {
-    const int kcsz = dtype != LGEN_F32 ? 32 : 16;
+    const int kcsz = kc_of(dtype);
     if (N % 16 || K % kcsz || M > MTs * 16 || passes < 1 || passes > 64) return LGEN_ERR_BAD_ARG;
     if ((norm_w && (ssq_parts < 1 || ssq_parts > LGEN_SSQ_STRIDE)) || (ssq_out && N / 16 > LGEN_SSQ_STRIDE)) return LGEN_ERR_BAD_ARG;
     GemmArgs a{};
@@ -356,7 +353,7 @@ static int qkv_rope_impl(const void* wp, const void* xp, void* q_out, void* k_ca
                          const int* pos_ptr, int pos_stride, int M, int MTs, int d, int n_head, int hd, int hdp, int S8,
                          int kv_row_stride, int dtype, int mt, int nt, int kw, const void* norm_w, const float* ssq_in,
                          int ssq_parts, float eps, int passes, void* stream) {
-    const int kcsz = dtype != LGEN_F32 ? 32 : 16;
+    const int kcsz = kc_of(dtype);
     if (d % kcsz || (3 * d) % 16 || hd % 4 || d != n_head * hd || M > MTs * 16 || pos_stride < 0 || pos_stride > 1 || passes < 1 ||
         passes > 64)
         return LGEN_ERR_BAD_ARG;
@@ -368,7 +365,7 @@ static int qkv_rope_impl(const void* wp, const void* xp, void* q_out, void* k_ca
     a.d = d; a.hd = hd; a.hdp = hdp; a.H = n_head; a.S8 = S8;
     a.kvs = kv_row_stride > 0 ? kv_row_stride : hdp;
     {   // rows may be packed tighter than the lane group hdp (lgen.h): at least hd rounded up to one 16-byte piece of the storage type
-        const int epl_ = kcsz / 4;
+        const int epl_ = epl_of(dtype);
         if (a.kvs < (hd + epl_ - 1) / epl_ * epl_ || a.kvs % epl_) return LGEN_ERR_BAD_ARG;
     }
     a.nw = (const uint4*)norm_w; a.ssq_in = ssq_in; a.parts = ssq_parts; a.eps = eps; a.inv_k = 1.0f / (float)d;

@@ -4,6 +4,8 @@
 //   lgen_rmsnorm      RMSNorm on the packed layout (gpt.py:137-148), two bf16 rounding points
 //   lgen_attn_decode  KV-cached single-query attention over kv_len = pos+1 keys only
 //                     (gpt.py:229-236 repeat_interleave + math-SDPA with causal_mask[:, pos])
+#include <utility>
+
 #include "gemm_epilogue.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -35,9 +37,8 @@ template <typename D>
 __global__ __launch_bounds__(256) void embed_pack_kernel(const uint4* __restrict__ table, const int* __restrict__ idx,
                                                          uint4* __restrict__ hp, float* __restrict__ ssq_out,
                                                          int* __restrict__ state, int M, int MTs, int d, int rows,
-                                                         const uint4* __restrict__ table0 = nullptr,
-                                                         const int* __restrict__ idx0 = nullptr,
-                                                         const int* __restrict__ row_pos = nullptr, int rows0 = 0) {
+                                                         const uint4* __restrict__ table0, const int* __restrict__ idx0,
+                                                         const int* __restrict__ row_pos, int rows0) {
     const int KCH = d / D::KC;
     const int total = KCH * MTs * 64;  // a multiple of 64: every wave is one (kc, mt) chunk
     if (state && blockIdx.x == 0 && threadIdx.x == 0) {
@@ -64,27 +65,23 @@ __global__ __launch_bounds__(256) void embed_pack_kernel(const uint4* __restrict
     }
 }
 
+// row m <- table[idx[m]], or table0[idx0[m]] where row_pos[m] == 0 (row_pos null: never)
+static int launch_embed_pack(const void* table, const int* idx, void* hp, float* ssq_out, int* state_advance, int M, int MTs, int d,
+                             int rows, const void* table0, const int* idx0, const int* row_pos, int rows0, int dtype, void* stream) {
+    if (M > MTs * 16 || d % 32 || (ssq_out && d / 16 > LGEN_SSQ_STRIDE)) return LGEN_ERR_BAD_ARG;
+    return lgen_dispatch_dtype(dtype, [&](auto tag) {
+        using D = decltype(tag);
+        const int total = (d / D::KC) * MTs * 64;
+        hipLaunchKernelGGL(embed_pack_kernel<D>, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const uint4*)table, idx,
+                           (uint4*)hp, ssq_out, state_advance, M, MTs, d, rows, (const uint4*)table0, idx0, row_pos, rows0);
+        LGEN_CHECK_LAUNCH();
+        return 0;
+    });
+}
+
 extern "C" int lgen_embed_pack(const void* table, const int* idx, void* hp, float* ssq_out, int* state_advance, int M,
                                int MTs, int d, int rows, int dtype, void* stream) {
-    if (M > MTs * 16 || d % 32 || (ssq_out && d / 16 > LGEN_SSQ_STRIDE)) return LGEN_ERR_BAD_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == LGEN_BF16) {
-        int total = (d / 32) * MTs * 64;
-        hipLaunchKernelGGL(embed_pack_kernel<BF16>, dim3((total + 255) / 256), dim3(256), 0, st, (const uint4*)table, idx,
-                           (uint4*)hp, ssq_out, state_advance, M, MTs, d, rows);
-    } else if (dtype == LGEN_F16) {
-        int total = (d / 32) * MTs * 64;
-        hipLaunchKernelGGL(embed_pack_kernel<F16>, dim3((total + 255) / 256), dim3(256), 0, st, (const uint4*)table, idx,
-                           (uint4*)hp, ssq_out, state_advance, M, MTs, d, rows);
-    } else if (dtype == LGEN_F32) {
-        int total = (d / 16) * MTs * 64;
-        hipLaunchKernelGGL(embed_pack_kernel<F32>, dim3((total + 255) / 256), dim3(256), 0, st, (const uint4*)table, idx,
-                           (uint4*)hp, ssq_out, state_advance, M, MTs, d, rows);
-    } else {
-        return LGEN_ERR_BAD_ARG;
-    }
-    LGEN_CHECK_LAUNCH();
-    return 0;
+    return launch_embed_pack(table, idx, hp, ssq_out, state_advance, M, MTs, d, rows, nullptr, nullptr, nullptr, 0, dtype, stream);
 }
 
 // Continuous batching (autoregressive/serve/: every row of the step batch is its own request at its own position): row m
@@ -93,25 +90,9 @@ extern "C" int lgen_embed_pack(const void* table, const int* idx, void* hp, floa
 extern "C" int lgen_embed_rows(const void* tok_table, const void* cls_table, const int* cur_tok, const int* cond,
                                const int* row_pos, void* hp, float* ssq_out, int M, int MTs, int d, int tok_rows, int cls_rows,
                                int dtype, void* stream) {
-    if (M > MTs * 16 || d % 32 || !row_pos) return LGEN_ERR_BAD_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == LGEN_BF16) {
-        int total = (d / 32) * MTs * 64;
-        hipLaunchKernelGGL(embed_pack_kernel<BF16>, dim3((total + 255) / 256), dim3(256), 0, st, (const uint4*)tok_table, cur_tok,
-                           (uint4*)hp, ssq_out, (int*)nullptr, M, MTs, d, tok_rows, (const uint4*)cls_table, cond, row_pos, cls_rows);
-    } else if (dtype == LGEN_F16) {
-        int total = (d / 32) * MTs * 64;
-        hipLaunchKernelGGL(embed_pack_kernel<F16>, dim3((total + 255) / 256), dim3(256), 0, st, (const uint4*)tok_table, cur_tok,
-                           (uint4*)hp, ssq_out, (int*)nullptr, M, MTs, d, tok_rows, (const uint4*)cls_table, cond, row_pos, cls_rows);
-    } else if (dtype == LGEN_F32) {
-        int total = (d / 16) * MTs * 64;
-        hipLaunchKernelGGL(embed_pack_kernel<F32>, dim3((total + 255) / 256), dim3(256), 0, st, (const uint4*)tok_table, cur_tok,
-                           (uint4*)hp, ssq_out, (int*)nullptr, M, MTs, d, tok_rows, (const uint4*)cls_table, cond, row_pos, cls_rows);
-    } else {
-        return LGEN_ERR_BAD_ARG;
-    }
-    LGEN_CHECK_LAUNCH();
-    return 0;
+    if (!row_pos) return LGEN_ERR_BAD_ARG;
+    return launch_embed_pack(tok_table, cur_tok, hp, ssq_out, nullptr, M, MTs, d, tok_rows, cls_table, cond, row_pos, cls_rows, dtype,
+                             stream);
 }
 
 // Row sums of squares of an already packed residual stream (t2i prefix rows enter the decode loop
@@ -128,22 +109,15 @@ __global__ __launch_bounds__(256) void ssq_pack_kernel(const uint4* __restrict__
 }
 
 extern "C" int lgen_ssq_pack(const void* hp, float* ssq_out, int MTs, int d, int dtype, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
     if (d % 32 || !ssq_out || d / 16 > LGEN_SSQ_STRIDE) return LGEN_ERR_BAD_ARG;
-    if (dtype == LGEN_BF16) {
-        int total = (d / 32) * MTs * 64;
-        hipLaunchKernelGGL(ssq_pack_kernel<BF16>, dim3((total + 255) / 256), dim3(256), 0, st, (const uint4*)hp, ssq_out, total, MTs);
-    } else if (dtype == LGEN_F16) {
-        int total = (d / 32) * MTs * 64;
-        hipLaunchKernelGGL(ssq_pack_kernel<F16>, dim3((total + 255) / 256), dim3(256), 0, st, (const uint4*)hp, ssq_out, total, MTs);
-    } else if (dtype == LGEN_F32) {
-        int total = (d / 16) * MTs * 64;
-        hipLaunchKernelGGL(ssq_pack_kernel<F32>, dim3((total + 255) / 256), dim3(256), 0, st, (const uint4*)hp, ssq_out, total, MTs);
-    } else {
-        return LGEN_ERR_BAD_ARG;
-    }
-    LGEN_CHECK_LAUNCH();
-    return 0;
+    return lgen_dispatch_dtype(dtype, [&](auto tag) {
+        using D = decltype(tag);
+        const int total = (d / D::KC) * MTs * 64;
+        hipLaunchKernelGGL(ssq_pack_kernel<D>, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const uint4*)hp, ssq_out,
+                           total, MTs);
+        LGEN_CHECK_LAUNCH();
+        return 0;
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -205,26 +179,29 @@ __global__ __launch_bounds__(1024) void rmsnorm_kernel(const uint4* __restrict__
     }
 }
 
+template <typename D, int RMS_MAXC>
+static int launch_rmsnorm(const void* hp, const void* weight, void* xnp, int MTs, int d, float eps, int nw, void* stream) {
+    hipLaunchKernelGGL((rmsnorm_kernel<D, RMS_MAXC>), dim3(MTs), dim3(64 * nw), 0, (hipStream_t)stream, (const uint4*)hp, weight,
+                       (uint4*)xnp, MTs, d, eps);
+    LGEN_CHECK_LAUNCH();
+    return 0;
+}
+
 extern "C" int lgen_rmsnorm(const void* hp, const void* weight, void* xnp, int MTs, int d, float eps, int dtype,
                             void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    const int kcsz = dtype != LGEN_F32 ? 32 : 16;
-    if (d % kcsz) return LGEN_ERR_BAD_ARG;
-    const int KCH = d / kcsz;
+    if (d % kc_of(dtype)) return LGEN_ERR_BAD_ARG;
+    const int KCH = d / kc_of(dtype);
     int nw = 4;
     while (nw < 16 && nw * 4 < KCH) nw *= 2;  // ~4 chunks per wave, at most 8 (16 for very wide rows)
     if (nw * 16 < KCH) return LGEN_ERR_BAD_ARG;
     const bool wide = nw * 8 < KCH;
     if (wide && dtype != LGEN_F32) return LGEN_ERR_UNSUPPORTED;  // 16-bit rows wider than 4096: 16 chunks per wave would spill (no registry model)
-#define LGEN_RMS(DT, C) hipLaunchKernelGGL((rmsnorm_kernel<DT, C>), dim3(MTs), dim3(64 * nw), 0, st, (const uint4*)hp, weight, \
-                                           (uint4*)xnp, MTs, d, eps)
-    if (dtype == LGEN_BF16) LGEN_RMS(BF16, 8);
-    else if (dtype == LGEN_F16) LGEN_RMS(F16, 8);
-    else if (dtype == LGEN_F32) { if (wide) LGEN_RMS(F32, 16); else LGEN_RMS(F32, 8); }
-    else return LGEN_ERR_BAD_ARG;
-#undef LGEN_RMS
-    LGEN_CHECK_LAUNCH();
-    return 0;
+    return lgen_dispatch_dtype(dtype, [&](auto tag) {
+        using D = decltype(tag);
+        if constexpr (D::ESZ == 4)   // the 16-chunk form is compiled for fp32 alone
+            if (wide) return launch_rmsnorm<D, 16>(hp, weight, xnp, MTs, d, eps, nw, stream);
+        return launch_rmsnorm<D, 8>(hp, weight, xnp, MTs, d, eps, nw, stream);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -253,6 +230,75 @@ struct AttnArgs {
     int mask_len;        // only keys < mask_len consult the mask row (t2i: the caption prefix); the rest is pure causal
 };
 
+// One group = CH wave-loads of K and of V = CH * KPL keys; both decode kernels below walk the keys of a (b, h) in such groups.
+// attn_load_group issues the loads of group g.  Row clamp smax: until the position is known the last slot of the slab (the first
+// group is requested before the position load resolves); from then on the last VISIBLE key, so that the lanes of a partly filled
+// last group re-read one line instead of fetching up to CH * KPL - 1 rows nobody looks at (round 5: on average 15.5 of 288.5 keys per
+// launch, 5 % of the kernel's HBM bytes -- the live PMC ratio 1.07 at positions 64 / 288 / 575 was exactly this).  live = false
+// (persistent kernel, look-ahead past its last item): kp / vp are the caller's dummy pointer and every load reads it at offset 0.
+template <int CH, int KPL>
+LGEN_DEV void attn_load_group(uint4 (&KB)[CH], uint4 (&VB)[CH], const uint4* kp, const uint4* vp, int g, int kin, int smax, int rpr,
+                              bool live) {
+#pragma unroll
+    for (int j = 0; j < CH; ++j) {
+        int kk = g * (CH * KPL) + j * KPL + kin;
+        kk = kk < smax ? kk : smax;
+        const size_t o = live ? (size_t)kk * rpr : 0;
+        KB[j] = ldg_nt(kp + o);
+        VB[j] = ldg_nt(vp + o);
+    }
+}
+
+// attn_fold_group folds the loaded group g into the running online-softmax state (m_run, l_run, acc) of this lane's key slot: one
+// wave-uniform running maximum per group.  pm: this row's mask bytes or null; keys >= kvlen are invisible.  The two forms of q . k:
+//   DOT8 = false  sum of fl(q sf) * fl(k sf) by fmaf: ATen's sqrt(scale) on both operands; qf = q * sf unpacked, qk_scale = sf
+//   DOT8 = true   16-bit storage only: packed dot products on the RAW operands (v_dot2c_f32_bf16 / v_dot2_f32_f16: 4 instructions
+//                 per 8 elements instead of 8 unpacks + 8 multiplies + 8 fmas), scaled once by qk_scale = sf^2; qraw = q as loaded.
+//                 The products of two 8- / 11-bit mantissas are exact in fp32, so this differs from the first form by fp32
+//                 round-off only, like any other summation order (and v_dot2 flushes fp32 accumulator denormals).
+template <typename D, int LPK, int CH, bool DOT8>
+LGEN_DEV void attn_fold_group(const uint4 (&KB)[CH], const uint4 (&VB)[CH], int g, int kin, int kvlen, const unsigned char* pm,
+                              int mask_len, const float (&qf)[D::EPL], const uint4& qraw, float qk_scale, float& m_run, float& l_run,
+                              float (&acc)[D::EPL]) {
+    constexpr int KPL = 64 / LPK, EPL = D::EPL;
+    float s[CH];
+    float tmax = -1e30f;
+#pragma unroll
+    for (int j = 0; j < CH; ++j) {
+        const int key = g * (CH * KPL) + j * KPL + kin;
+        float dot = 0.f;
+        if constexpr (DOT8) {
+            dot = D::dot8(KB[j], qraw) * qk_scale;
+        } else {
+            float kf[EPL];
+            D::unpack(KB[j], kf);
+#pragma unroll
+            for (int e = 0; e < EPL; ++e) dot = fmaf(qf[e], kf[e] * qk_scale, dot);
+        }
+        dot = group_sum<LPK>(dot);
+        bool vis = key < kvlen;
+        if (pm && vis && key < mask_len) vis = pm[key] != 0;
+        s[j] = vis ? dot : -1e30f;
+        tmax = fmaxf(tmax, s[j]);
+    }
+    tmax = across_groups<LPK>(tmax, [](float x, float y) { return fmaxf(x, y); });
+    const float m_new = fmaxf(m_run, tmax);
+    const float scale = D::fexp(m_run - m_new);
+    l_run *= scale;
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) acc[e] *= scale;
+#pragma unroll
+    for (int j = 0; j < CH; ++j) {
+        const float p = s[j] > -1e29f ? D::fexp(s[j] - m_new) : 0.f;
+        l_run += p;
+        float vf[EPL];
+        D::unpack(VB[j], vf);
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) acc[e] = fmaf(p, vf[e], acc[e]);
+    }
+    m_run = m_new;
+}
+
 // HPW (round 3): (batch row, head) pairs per workgroup.  At 256 chain rows the grid is 4096 (b, h) pairs; dispatching that many
 // 128-thread workgroups is 9 us of a 52 us average launch (kv_len 1: 9.0 us at 256 rows against 4.6 us at 64), so wide chains put
 // 2 or 4 heads of one row into a workgroup (same kv_len: the waves stay balanced across the one barrier).
@@ -274,26 +320,14 @@ __global__ __launch_bounds__(64 * ATT_NW * HPW, (ATT_CH <= 2 ? 4 : 2)) void attn
     const int rpr = a.kvs / EPL;             // 16-byte pieces between consecutive rows of one cache
     const uint4* kp = (const uint4*)a.kc + rowbase * rpr + part;
     const uint4* vp = (const uint4*)a.vc + rowbase * rpr + part;
-    // Row clamp of the key loads.  Until the position is known: the last slot of the slab (the first group is requested before the
-    // position load resolves).  From then on: the last VISIBLE key, so that the lanes of a partly filled last group re-read one
-    // line instead of fetching up to GK - 1 rows nobody looks at (round 5: on average 15.5 of 288.5 keys per launch, 5 % of the
-    // kernel's HBM bytes -- the live PMC ratio 1.07 at positions 64 / 288 / 575 was exactly this).
-    int smax = a.S8 - 1;
+    int smax = a.S8 - 1;                     // row clamp of the key loads (attn_load_group)
 
     uint4 k0[ATT_CH], v0[ATT_CH], k1[ATT_CH], v1[ATT_CH];
-#define ATT_LOAD(KB, VB, g)                                                 \
-    {                                                                       \
-        _Pragma("unroll") for (int j = 0; j < ATT_CH; ++j) {                \
-            int kk = (g) * GK + j * KPL + kin;                              \
-            kk = kk < smax ? kk : smax;                                     \
-            KB[j] = ldg_nt(kp + (size_t)kk * rpr);                          \
-            VB[j] = ldg_nt(vp + (size_t)kk * rpr);                          \
-        }                                                                   \
-    }
+    auto load = [&](uint4 (&KB)[ATT_CH], uint4 (&VB)[ATT_CH], int g) { attn_load_group<ATT_CH, KPL>(KB, VB, kp, vp, g, kin, smax, rpr, true); };
     // group g of this wave: g = wv, wv + NW, ...; first group requested before pos is known
     int g = wv;
     const uint4 qv = ((const uint4*)a.q)[((size_t)b * a.H + h) * lpr + part];
-    ATT_LOAD(k0, v0, g);
+    load(k0, v0, g);
     const int pos = a.pos_ptr[b * a.pos_stride];
     const int kvlen = pos + 1;
     const int ngroups = (kvlen + GK - 1) / GK;
@@ -307,48 +341,18 @@ __global__ __launch_bounds__(64 * ATT_NW * HPW, (ATT_CH <= 2 ? 4 : 2)) void attn
     float m_run = -1e30f, l_run = 0.f, acc[EPL];
 #pragma unroll
     for (int e = 0; e < EPL; ++e) acc[e] = 0.f;
-
-#define ATT_COMPUTE(KB, VB, g)                                                                     \
-    {                                                                                              \
-        float s[ATT_CH];                                                                           \
-        float tmax = -1e30f;                                                                       \
-        _Pragma("unroll") for (int j = 0; j < ATT_CH; ++j) {                                       \
-            const int key = (g) * GK + j * KPL + kin;                                              \
-            float kf[EPL];                                                                         \
-            D::unpack(KB[j], kf);                                                                  \
-            float dot = 0.f;                                                                       \
-            _Pragma("unroll") for (int e = 0; e < EPL; ++e) dot = fmaf(qf[e], kf[e] * a.sf, dot);  \
-            dot = group_sum<LPK>(dot);                                                             \
-            bool vis = key < kvlen;                                                                \
-            if (pm && vis && key < a.mask_len) vis = pm[key] != 0;                                 \
-            s[j] = vis ? dot : -1e30f;                                                             \
-            tmax = fmaxf(tmax, s[j]);                                                              \
-        }                                                                                          \
-        tmax = across_groups<LPK>(tmax, [](float x, float y) { return fmaxf(x, y); });              \
-        const float m_new = fmaxf(m_run, tmax);                                                    \
-        const float scale = D::fexp(m_run - m_new);                                                \
-        l_run *= scale;                                                                            \
-        _Pragma("unroll") for (int e = 0; e < EPL; ++e) acc[e] *= scale;                           \
-        _Pragma("unroll") for (int j = 0; j < ATT_CH; ++j) {                                       \
-            const float p = s[j] > -1e29f ? D::fexp(s[j] - m_new) : 0.f;                           \
-            l_run += p;                                                                            \
-            float vf[EPL];                                                                         \
-            D::unpack(VB[j], vf);                                                                  \
-            _Pragma("unroll") for (int e = 0; e < EPL; ++e) acc[e] = fmaf(p, vf[e], acc[e]);       \
-        }                                                                                          \
-        m_run = m_new;                                                                             \
-    }
+    auto fold = [&](const uint4 (&KB)[ATT_CH], const uint4 (&VB)[ATT_CH], int g) {   // every storage type: the fmaf form of q . k
+        attn_fold_group<D, LPK, ATT_CH, false>(KB, VB, g, kin, kvlen, pm, a.mask_len, qf, qv, a.sf, m_run, l_run, acc);
+    };
     while (g < ngroups) {
-        if (g + ATT_NW < ngroups) ATT_LOAD(k1, v1, g + ATT_NW);
-        ATT_COMPUTE(k0, v0, g);
+        if (g + ATT_NW < ngroups) load(k1, v1, g + ATT_NW);
+        fold(k0, v0, g);
         g += ATT_NW;
         if (g >= ngroups) break;
-        if (g + ATT_NW < ngroups) ATT_LOAD(k0, v0, g + ATT_NW);
-        ATT_COMPUTE(k1, v1, g);
+        if (g + ATT_NW < ngroups) load(k0, v0, g + ATT_NW);
+        fold(k1, v1, g);
         g += ATT_NW;
     }
-#undef ATT_LOAD
-#undef ATT_COMPUTE
     // combine the KPL key groups of this wave (lanes with equal `part`)
 #pragma unroll
     for (int o = LPK; o < 64; o <<= 1) {
@@ -411,9 +415,13 @@ extern "C" int lgen_ssq_group4(const float* ssq_in, float* ssq_out, int rows, in
 }
 
 // ---- persistent form (round 4, variant 8) ---------------------------------------------------------------------------------
-// Same arithmetic per (batch row, head) as attn_decode_kernel with one wave per item (the wave-level online softmax of variants
-// 4 / 5: every group of CH x KPL keys updates one wave-uniform running maximum, so the result does not depend on how many waves
-// share the chip), different schedule: a fixed grid of NWV-wave workgroups, ONE per CU, whose waves each walk whole (b, h) items
+// The online softmax per (batch row, head) of attn_decode_kernel with one wave per item (variants 4 / 5: every group of CH x KPL
+// keys updates one wave-uniform running maximum, so the result does not depend on how many waves share the chip).  For fp32
+// storage that is the same arithmetic; for bf16 / fp16 storage this kernel forms q . k with packed dot products on the raw
+// operands and one scale by sf^2 (attn_fold_group, DOT8) where the workgroup kernel sums fl(q sf) * fl(k sf), so the two
+// differ by fp32 round-off (and v_dot2 flushes fp32 accumulator denormals): the kernel spent 44 % of its wave cycles issuing
+// VALU (profiles/r06_sq_pmc.csv) -- cycles the other chain's GEMM waves on the same SIMDs wait for.
+// Different schedule: a fixed grid of NWV-wave workgroups, ONE per CU, whose waves each walk whole (b, h) items
 // gw, gw + total_waves, ... as ONE flat stream of K/V groups -- the loads of the next group (of the next item, at an item
 // boundary) are in flight while the current group is reduced, 2 x 2 x CH KiB per wave.  Why (measured, round 4):
 //   * at 256 rows attn_decode_kernel is 2048 workgroups of 4 waves that fill every SIMD to 5 waves: ~9 us of a 52 us launch are
@@ -434,7 +442,7 @@ __global__ __launch_bounds__(64 * NWV) void attn_decode_persist_kernel(AttnArgs 
     const int part = lane % LPK, kin = lane / LPK;
     const int lpr = a.hdp / EPL;             // 16-byte pieces per key row (== LPK)
     const int rpr = a.kvs / EPL;             // 16-byte pieces between consecutive rows of one cache
-    int smax = a.S8 - 1;                    // row clamp of the key loads: the last slot until the position is known, then the last visible key (see attn_decode_kernel)
+    int smax = a.S8 - 1;                     // row clamp of the key loads (attn_load_group)
     const uint4* const dummy = (const uint4*)a.q + part;   // where the look-ahead loads past the last item point (finite, L2-hot)
 
     uint4 k0[CH], v0[CH], k1[CH], v1[CH];
@@ -442,14 +450,7 @@ __global__ __launch_bounds__(64 * NWV) void attn_decode_persist_kernel(AttnArgs 
         const bool live = item < items;      // wave-uniform; loads stay unconditional so that the waits stay counted
         const uint4* kp = live ? (const uint4*)a.kc + (size_t)item * a.S8 * rpr + part : dummy;
         const uint4* vp = live ? (const uint4*)a.vc + (size_t)item * a.S8 * rpr + part : dummy;
-#pragma unroll
-        for (int j = 0; j < CH; ++j) {
-            int kk = g * GK + j * KPL + kin;
-            kk = kk < smax ? kk : smax;
-            const size_t o = live ? (size_t)kk * rpr : 0;
-            KB[j] = ldg_nt(kp + o);
-            VB[j] = ldg_nt(vp + o);
-        }
+        attn_load_group<CH, KPL>(KB, VB, kp, vp, g, kin, smax, rpr, live);
     };
     // the first group and q of the first item are requested before the position is known
     load(k0, v0, gw, 0);
@@ -467,14 +468,10 @@ __global__ __launch_bounds__(64 * NWV) void attn_decode_persist_kernel(AttnArgs 
     int ci = gw, cg = 0;                      // compute cursor
     float qf[EPL], m_run = -1e30f, l_run = 0.f, acc[EPL];
     uint4 qn = qv, qraw = qv;
-    // 16-bit storage (round 6): q . k as packed dot products on the RAW operands (v_dot2c_f32_bf16 / v_dot2_f32_f16: 4 instructions
-    // per 8 elements instead of 8 unpacks + 8 multiplies + 8 fmas), scaled once by sf^2 -- the products of two 8- / 11-bit
-    // mantissas are exact in fp32, so this differs from the reference's sum of fl(q sf) * fl(k sf) (ATen's sqrt(scale) on both operands)
-    // by fp32 round-off only, like any other summation order.  The kernel spent 44 % of its wave cycles issuing VALU
-    // (profiles/r06_sq_pmc.csv) -- cycles the other chain's GEMM waves on the same SIMDs wait for.
-    const float sf2 = a.sf * a.sf;
+    constexpr bool DOT8 = D::ESZ == 2;       // 16-bit storage (round 6): the packed-dot form of q . k, see attn_fold_group
+    const float qk_scale = DOT8 ? a.sf * a.sf : a.sf;
     auto begin_item = [&]() {
-        if constexpr (D::ESZ == 2) {
+        if constexpr (DOT8) {
             qraw = qn;
         } else {
             D::unpack(qn, qf);
@@ -488,44 +485,9 @@ __global__ __launch_bounds__(64 * NWV) void attn_decode_persist_kernel(AttnArgs 
         qn = ((const uint4*)a.q)[(size_t)(nxt < items ? nxt : ci) * lpr + part];
     };
     begin_item();
-    auto compute = [&](const uint4 (&KB)[CH], const uint4 (&VB)[CH]) {
+    auto fold = [&](const uint4 (&KB)[CH], const uint4 (&VB)[CH]) {
         const unsigned char* pm = a.mask ? a.mask + ((size_t)(ci / a.H) * a.S8 + pos) * a.S8 : nullptr;
-        float s[CH];
-        float tmax = -1e30f;
-#pragma unroll
-        for (int j = 0; j < CH; ++j) {
-            const int key = cg * GK + j * KPL + kin;
-            float dot = 0.f;
-            if constexpr (D::ESZ == 2) {
-                dot = D::dot8(KB[j], qraw) * sf2;
-            } else {
-                float kf[EPL];
-                D::unpack(KB[j], kf);
-#pragma unroll
-                for (int e = 0; e < EPL; ++e) dot = fmaf(qf[e], kf[e] * a.sf, dot);
-            }
-            dot = group_sum<LPK>(dot);
-            bool vis = key < kvlen;
-            if (pm && vis && key < a.mask_len) vis = pm[key] != 0;
-            s[j] = vis ? dot : -1e30f;
-            tmax = fmaxf(tmax, s[j]);
-        }
-        tmax = across_groups<LPK>(tmax, [](float x, float y) { return fmaxf(x, y); });
-        const float m_new = fmaxf(m_run, tmax);
-        const float scale = D::fexp(m_run - m_new);
-        l_run *= scale;
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) acc[e] *= scale;
-#pragma unroll
-        for (int j = 0; j < CH; ++j) {
-            const float p = s[j] > -1e29f ? D::fexp(s[j] - m_new) : 0.f;
-            l_run += p;
-            float vf[EPL];
-            D::unpack(VB[j], vf);
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) acc[e] = fmaf(p, vf[e], acc[e]);
-        }
-        m_run = m_new;
+        attn_fold_group<D, LPK, CH, DOT8>(KB, VB, cg, kin, kvlen, pm, a.mask_len, qf, qraw, qk_scale, m_run, l_run, acc);
     };
     auto end_group = [&]() {                  // returns false when this wave has no item left
         if (++cg < ngroups) return true;
@@ -551,103 +513,95 @@ __global__ __launch_bounds__(64 * NWV) void attn_decode_persist_kernel(AttnArgs 
     while (true) {
         load(k1, v1, li, lg);
         advance(li, lg);
-        compute(k0, v0);
+        fold(k0, v0);
         if (!end_group()) break;
         load(k0, v0, li, lg);
         advance(li, lg);
-        compute(k1, v1);
+        fold(k1, v1);
         if (!end_group()) break;
     }
 }
 
-// Kernel variants (explicit `variant` argument of lgen_attn_decode; -1 = the library's choice by shape):
-//   (K/V loads per buffer, waves per (b, h) workgroup): 0 = (4, 4); 1 = (2, 4); 2 = (2, 2): 128-thread workgroups, lowest fixed cost at
-//   <= 128 rows (4.4 us at kv_len 1 vs 6.1 us with 4 waves, same 6.4 TB/s incremental rate); 3 = (4, 2); 4 = (2, 1); 5 = (4, 1);
-//   6 / 7 (round 3): (2, 2) with 2 / 4 heads of a row per workgroup (fewer workgroups to dispatch at >= 256 rows);
-//   8 .. 13 (round 4): the persistent form, (loads per buffer, waves per workgroup) = 8: (4, 8); 9: (4, 8) x two workgroups per CU;
-//   10: (4, 4); 11: (2, 8); 12: (2, 4); 13: (1, 8); 14: (3, 4) -- one position for all rows only.
+// What the explicit `variant` argument of lgen_attn_decode selects (-1 = the library's choice by shape, attn_decode_impl).
+//   workgroup form  (attn_decode_kernel):         ch K/V loads per buffer, nw waves per (b, h), hpw (b, h) pairs per workgroup
+//   persistent form (attn_decode_persist_kernel): ch K/V loads per buffer, nw waves per workgroup, wg_per_cu workgroups per CU; one
+//     position for all rows only.  Bytes in flight per CU = waves x 4 x ch KiB: what the HBM queue holds beyond the
+//     bandwidth-delay product (~10 MB chip-wide) only adds latency for every kernel that shares the chip.
 // K/V loads are non-temporal (ldg_nt): every cache row is read once per step, and keeping 75-150 MB per layer out of the
 // memory-side cache leaves the (chain-shared) weights there: 26.5 vs 28.5 us at kv_len 576, 71.6 vs 68.6 img/s.  Fixed at
 // compile time: a per-load run-time choice costs the compiler its count of loads in flight (vmcnt(0) before every compute).
+struct AttnVariant {
+    bool persistent;
+    int ch, nw, hpw, wg_per_cu;
+};
+constexpr AttnVariant ATTN_VARIANTS[] = {
+    {false, 4, 4, 1, 0},   //  0
+    {false, 2, 4, 1, 0},   //  1
+    {false, 2, 2, 1, 0},   //  2: 128-thread workgroups, lowest fixed cost at <= 128 rows (4.4 us at kv_len 1 vs 6.1 us with 4 waves, same
+                           //     6.4 TB/s incremental rate)
+    {false, 4, 2, 1, 0},   //  3
+    {false, 2, 1, 1, 0},   //  4
+    {false, 4, 1, 1, 0},   //  5
+    {false, 2, 2, 2, 0},   //  6 (round 3): fewer workgroups to dispatch at >= 256 rows: 49.8 vs 50.7 us average launch at 256 rows, 27.3 vs
+                           //     27.0 at 128 (tools/attn_sweep.py, profiles/r03_attn_sweep.log)
+    {false, 2, 2, 4, 0},   //  7 (round 3)
+    {true, 4, 8, 1, 1},    //  8 (round 4)
+    {true, 4, 8, 1, 2},    //  9: the kernel of 8, two workgroups per CU
+    {true, 4, 4, 1, 1},    // 10: 4 waves x 16 KiB in flight per CU.  Alone ~6 % slower than variant 6 (54.3 vs 51.1 us per average launch
+                           //     at 256 rows: one wave per SIMD has nothing to hide its own VALU latency behind), but with two chains in
+                           //     flight the bench gains 8 % (110.1 -> 119.0 img/s at 512-row chains): 64 KB per CU in flight instead of 160
+                           //     leaves the HBM queue short enough for the other chain's latency-bound kernels, and 4 resident waves leave
+                           //     every SIMD room for them (tools/overlap_probe.py: the GEMM chain hidden under an attention chain 0.30 -> 0.57)
+    {true, 2, 8, 1, 1},    // 11
+    {true, 2, 4, 1, 1},    // 12
+    {true, 1, 8, 1, 1},    // 13
+    {true, 3, 4, 1, 1},    // 14
+};
+constexpr int ATTN_NVARIANTS = sizeof(ATTN_VARIANTS) / sizeof(ATTN_VARIANTS[0]);
+
+// launch geometry and kernel instantiation of table entry V (two entries with equal template arguments share one kernel)
+template <typename D, int LPK, int V>
+static void launch_attn_variant(const AttnArgs& a, int B2, hipStream_t st) {
+    constexpr AttnVariant v = ATTN_VARIANTS[V];
+    if constexpr (v.persistent) {
+        const int items = B2 * a.H;
+        int wgs = lgen_cu_count() * v.wg_per_cu;
+        if (wgs * v.nw > items) wgs = (items + v.nw - 1) / v.nw;
+        hipLaunchKernelGGL((attn_decode_persist_kernel<D, LPK, v.ch, v.nw>), dim3(wgs), dim3(64 * v.nw), 0, st, a, items, wgs * v.nw);
+    } else {
+        hipLaunchKernelGGL((attn_decode_kernel<D, LPK, v.ch, v.nw, v.hpw>), dim3(B2 * a.H / v.hpw), dim3(64 * v.nw * v.hpw), 0, st, a);
+    }
+}
+template <typename D, int LPK, int... V>
+static void launch_attn_decode(int variant, std::integer_sequence<int, V...>, const AttnArgs& a, int B2, hipStream_t st) {
+    ((variant == V ? launch_attn_variant<D, LPK, V>(a, B2, st) : (void)0), ...);
+}
+
 static int attn_decode_impl(const void* q, const void* k_cache, const void* v_cache, void* out_packed,
                             const int* pos_ptr, int pos_stride, const unsigned char* mask, int mask_len, int B2, int MTs,
-                            int n_head, int hd, int hdp, int S8, int kv_row_stride, int dtype, int variant_arg, void* stream) {
+                            int n_head, int hd, int hdp, int S8, int kv_row_stride, int dtype, int variant, void* stream) {
     AttnArgs a{q, k_cache, v_cache, out_packed, pos_ptr, pos_stride, mask, n_head, hd, hdp, S8, MTs, 0.f,
                kv_row_stride > 0 ? kv_row_stride : hdp, mask_len > 0 ? mask_len : S8};
-    if (variant_arg < -1 || variant_arg > 14) return LGEN_ERR_BAD_ARG;
+    if (variant < -1 || variant >= ATTN_NVARIANTS) return LGEN_ERR_BAD_ARG;
     a.sf = sqrtf(1.0f / sqrtf((float)hd));
-    hipStream_t st = (hipStream_t)stream;
-    const int epl = dtype != LGEN_F32 ? 8 : 4;
-    if (dtype != LGEN_BF16 && dtype != LGEN_F32 && dtype != LGEN_F16) return LGEN_ERR_BAD_ARG;
+    const int epl = epl_of(dtype);
     if (hdp % epl || hd > hdp || B2 > MTs * 16 || S8 < 1 || a.kvs < (hd + epl - 1) / epl * epl || a.kvs % epl) return LGEN_ERR_BAD_ARG;
-    const int lpk = hdp / epl;
-    // default variant 2; chains of >= 256 rows put two heads of a row into a workgroup (variant 6: 49.8 vs 50.7 us average launch
-    // at 256 rows, 27.3 vs 27.0 at 128: tools/attn_sweep.py, profiles/r03_attn_sweep.log)
-    // library's choice (variant_arg == -1): variant 2 below 256 rows; chains of >= 256 rows at one position take the persistent form with 4 waves x 16 KiB in flight per
-    // CU (variant 10).  Alone it is ~6 % slower than variant 6 (54.3 vs 51.1 us per average launch at 256 rows: one wave per SIMD
-    // has nothing to hide its own VALU latency behind), but with two chains in flight the bench gains 8 % (110.1 -> 119.0 img/s at
-    // 512-row chains, gpurun_out/attn_ab3.log): 64 KB per CU in flight instead of 160 leaves the HBM queue short enough for the other
-    // chain's latency-bound kernels, and 4 resident waves leave every SIMD room for them (tools/overlap_probe.py: the GEMM chain
-    // hidden under an attention chain 0.30 -> 0.57).  Per-row positions (continuous batching): variant 6 (two heads per workgroup).
-    int variant = variant_arg;
+    // the library's choice: variant 2 below 256 rows; from 256 rows the persistent variant 10 at one position for all rows, else
+    // (per-row positions: continuous batching) two heads per workgroup (variant 6) where the head count allows
     if (variant < 0) variant = B2 >= 256 ? (pos_stride == 0 ? 10 : (n_head % 2 == 0 ? 6 : 2)) : 2;
-    if (variant >= 8 && pos_stride == 0) {
-        // persistent form, (K/V loads per buffer CH, waves per workgroup) = 8: (4, 8), one workgroup per CU; 9: (4, 8) x two per CU;
-        // 10: (4, 4); 11: (2, 8); 12: (2, 4); 13: (1, 8).  Bytes in flight per CU = waves x 4 x CH KiB: what the HBM queue holds
-        // beyond the bandwidth-delay product (~10 MB chip-wide) only adds latency for every kernel that shares the chip.
-        const int n_cu = lgen_cu_count();
-        const int items = B2 * n_head;
-        const int nwv = (variant == 10 || variant == 12 || variant == 14) ? 4 : 8;
-        const int ch = variant == 14 ? 3 : (variant <= 10 ? 4 : (variant <= 12 ? 2 : 1));
-        int wgs = n_cu * (variant == 9 ? 2 : 1);
-        if (wgs * nwv > items) wgs = (items + nwv - 1) / nwv;
-        const int total_waves = wgs * nwv;
-#define LGEN_ATTP(DT, L)                                                                                                   \
-        do {                                                                                                               \
-            if (ch == 4 && nwv == 8) hipLaunchKernelGGL((attn_decode_persist_kernel<DT, L, 4, 8>), dim3(wgs), dim3(512), 0, st, a, items, total_waves); \
-            else if (ch == 4) hipLaunchKernelGGL((attn_decode_persist_kernel<DT, L, 4, 4>), dim3(wgs), dim3(256), 0, st, a, items, total_waves);        \
-            else if (ch == 3) hipLaunchKernelGGL((attn_decode_persist_kernel<DT, L, 3, 4>), dim3(wgs), dim3(256), 0, st, a, items, total_waves);        \
-            else if (ch == 2 && nwv == 8) hipLaunchKernelGGL((attn_decode_persist_kernel<DT, L, 2, 8>), dim3(wgs), dim3(512), 0, st, a, items, total_waves); \
-            else if (ch == 2) hipLaunchKernelGGL((attn_decode_persist_kernel<DT, L, 2, 4>), dim3(wgs), dim3(256), 0, st, a, items, total_waves);        \
-            else hipLaunchKernelGGL((attn_decode_persist_kernel<DT, L, 1, 8>), dim3(wgs), dim3(512), 0, st, a, items, total_waves);                     \
-        } while (0)
-        if (dtype == LGEN_BF16 && lpk == 8) LGEN_ATTP(BF16, 8);
-        else if (dtype == LGEN_BF16 && lpk == 16) LGEN_ATTP(BF16, 16);
-        else if (dtype == LGEN_F16 && lpk == 8) LGEN_ATTP(F16, 8);
-        else if (dtype == LGEN_F16 && lpk == 16) LGEN_ATTP(F16, 16);
-        else if (dtype == LGEN_F32 && lpk == 16) LGEN_ATTP(F32, 16);
-        else if (dtype == LGEN_F32 && lpk == 32) LGEN_ATTP(F32, 32);
+    const AttnVariant& v = ATTN_VARIANTS[variant];
+    return lgen_dispatch_dtype(dtype, [&](auto tag) {
+        using D = decltype(tag);
+        if (v.persistent && pos_stride != 0) return LGEN_ERR_UNSUPPORTED;   // per-row positions: the persistent form has one kv_len for all rows
+        if (n_head % v.hpw) return LGEN_ERR_BAD_ARG;
+        constexpr auto all = std::make_integer_sequence<int, ATTN_NVARIANTS>{};
+        // lanes per key = hdp / EPL: 8 | 16 (16-bit storage), 16 | 32 (fp32)
+        if (hdp == 64) launch_attn_decode<D, 64 / D::EPL>(variant, all, a, B2, (hipStream_t)stream);
+        else if (hdp == 128) launch_attn_decode<D, 128 / D::EPL>(variant, all, a, B2, (hipStream_t)stream);
         else return LGEN_ERR_BAD_ARG;
-#undef LGEN_ATTP
         LGEN_CHECK_LAUNCH();
         return 0;
-    }
-    const int hpw = variant == 6 ? 2 : (variant == 7 ? 4 : 1);
-    if (variant >= 8) return LGEN_ERR_UNSUPPORTED;   // per-row positions: the persistent form has one kv_len for all rows
-    if (n_head % hpw) return LGEN_ERR_BAD_ARG;
-    const int nw = variant >= 6 ? 2 : (variant >= 4 ? 1 : (variant >= 2 ? 2 : 4));
-    dim3 grid(B2 * n_head / hpw), block(64 * nw * hpw);
-#define LGEN_ATT(DT, L)                                                                              \
-    do {                                                                                             \
-        if (variant == 1) hipLaunchKernelGGL((attn_decode_kernel<DT, L, 2, 4, 1>), grid, block, 0, st, a);      \
-        else if (variant == 2) hipLaunchKernelGGL((attn_decode_kernel<DT, L, 2, 2, 1>), grid, block, 0, st, a); \
-        else if (variant == 3) hipLaunchKernelGGL((attn_decode_kernel<DT, L, 4, 2, 1>), grid, block, 0, st, a); \
-        else if (variant == 4) hipLaunchKernelGGL((attn_decode_kernel<DT, L, 2, 1, 1>), grid, block, 0, st, a); \
-        else if (variant == 5) hipLaunchKernelGGL((attn_decode_kernel<DT, L, 4, 1, 1>), grid, block, 0, st, a); \
-        else if (variant == 6) hipLaunchKernelGGL((attn_decode_kernel<DT, L, 2, 2, 2>), grid, block, 0, st, a); \
-        else if (variant == 7) hipLaunchKernelGGL((attn_decode_kernel<DT, L, 2, 2, 4>), grid, block, 0, st, a); \
-        else hipLaunchKernelGGL((attn_decode_kernel<DT, L, 4, 4, 1>), grid, block, 0, st, a);                          \
-    } while (0)
-    if (dtype == LGEN_BF16 && lpk == 8) LGEN_ATT(BF16, 8);
-    else if (dtype == LGEN_BF16 && lpk == 16) LGEN_ATT(BF16, 16);
-    else if (dtype == LGEN_F16 && lpk == 8) LGEN_ATT(F16, 8);
-    else if (dtype == LGEN_F16 && lpk == 16) LGEN_ATT(F16, 16);
-    else if (dtype == LGEN_F32 && lpk == 16) LGEN_ATT(F32, 16);
-    else if (dtype == LGEN_F32 && lpk == 32) LGEN_ATT(F32, 32);
-    else return LGEN_ERR_BAD_ARG;
-#undef LGEN_ATT
-    LGEN_CHECK_LAUNCH();
-    return 0;
+    });
 }
 
 extern "C" int lgen_attn_decode(const void* q, const void* k_cache, const void* v_cache, void* out_packed,
@@ -719,29 +673,19 @@ __global__ __launch_bounds__(256) void rope_append_prefill_kernel(const uint4* _
 extern "C" int lgen_rope_append_prefill(const void* qkv_packed, void* q_rows, void* k_cache, void* v_cache, const float* freqs,
                                         int R, int B2, int MTs, int d, int n_head, int hd, int hdp, int S8, int kv_row_stride,
                                         int pos0, int dtype, void* stream) {
-    const int kcsz = dtype != LGEN_F32 ? 32 : 16;
+    const int kcsz = kc_of(dtype), epl = epl_of(dtype);
     if ((3 * d) % kcsz || d != n_head * hd || hd % 2 || R > MTs * 16 || B2 < 1 || R % B2) return LGEN_ERR_BAD_ARG;
     const int kvs = kv_row_stride > 0 ? kv_row_stride : hdp;
-    {   // same key-row contract as lgen_attn_decode: whole 16-byte pieces, at least the head's valid elements apart
-        const int epl = dtype != LGEN_F32 ? 8 : 4;
-        if (kvs % epl || kvs < (hd + epl - 1) / epl * epl) return LGEN_ERR_BAD_ARG;
-    }
+    // same key-row contract as lgen_attn_decode: whole 16-byte pieces, at least the head's valid elements apart
+    if (kvs % epl || kvs < (hd + epl - 1) / epl * epl) return LGEN_ERR_BAD_ARG;
     const long long total = (long long)(3 * d / kcsz) * MTs * 64;
     const int blocks = (int)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == LGEN_BF16)
-        hipLaunchKernelGGL(rope_append_prefill_kernel<BF16>, dim3(blocks), dim3(256), 0, st, (const uint4*)qkv_packed, q_rows, k_cache,
-                           v_cache, freqs, R, B2, MTs, d, n_head, hd, hdp, S8, kvs, pos0);
-    else if (dtype == LGEN_F16)
-        hipLaunchKernelGGL(rope_append_prefill_kernel<F16>, dim3(blocks), dim3(256), 0, st, (const uint4*)qkv_packed, q_rows, k_cache,
-                           v_cache, freqs, R, B2, MTs, d, n_head, hd, hdp, S8, kvs, pos0);
-    else if (dtype == LGEN_F32)
-        hipLaunchKernelGGL(rope_append_prefill_kernel<F32>, dim3(blocks), dim3(256), 0, st, (const uint4*)qkv_packed, q_rows, k_cache,
-                           v_cache, freqs, R, B2, MTs, d, n_head, hd, hdp, S8, kvs, pos0);
-    else
-        return LGEN_ERR_BAD_ARG;
-    LGEN_CHECK_LAUNCH();
-    return 0;
+    return lgen_dispatch_dtype(dtype, [&](auto tag) {
+        hipLaunchKernelGGL(rope_append_prefill_kernel<decltype(tag)>, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+                           (const uint4*)qkv_packed, q_rows, k_cache, v_cache, freqs, R, B2, MTs, d, n_head, hd, hdp, S8, kvs, pos0);
+        LGEN_CHECK_LAUNCH();
+        return 0;
+    });
 }
 
 #define PF_MAXT 128
@@ -1040,85 +984,49 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(const uint16_t* 
 static int g_prefill_mfma = 1;
 extern "C" int lgen_debug_set_prefill_mfma(int v) { g_prefill_mfma = v ? 1 : 0; return 0; }
 
+// the two VALU forms: K/V of one (b, h) whole in LDS (T <= PF_MAXT), else key-tiled
 template <typename D>
-static int launch_attn_prefill_tiled(const void* q_rows, const void* k_cache, const void* v_cache, void* out_packed,
-                                     const unsigned char* mask, int T, int B2, int MTs, int n_head, int hd, int hdp, int S8, int kvs,
-                                     float sf, hipStream_t st) {
+static int launch_attn_prefill(const void* q_rows, const void* k_cache, const void* v_cache, void* out_packed,
+                               const unsigned char* mask, int T, int B2, int MTs, int n_head, int hd, int hdp, int S8, int kvs,
+                               float sf, hipStream_t st) {
+    auto launch = [&](auto kernel, dim3 grid, size_t lds, auto... tail) {
+        if (lds > 160 * 1024) return LGEN_ERR_BAD_ARG;
+        if (lds > 64 * 1024) {
+            hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return (int)e;
+        }
+        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, q_rows, k_cache, v_cache, out_packed, mask, T, B2, MTs, n_head, hd, hdp, S8,
+                           kvs, sf, tail...);
+        LGEN_CHECK_LAUNCH();
+        return 0;
+    };
+    if (T <= PF_MAXT)
+        return launch(attn_prefill_kernel<D>, dim3(B2 * n_head), ((size_t)2 * T * (hd + 1) + 4 * PF_MAXT + 4 * hd) * sizeof(float));
     int qt = 32;
     auto lds_for = [&](int q) { return ((size_t)2 * PFT_KT * (hd + 1) + (size_t)2 * q * hd + 4 * PFT_KT + 2 * q) * sizeof(float); };
     while (qt > 4 && lds_for(qt) > 160 * 1024) qt >>= 1;
-    const size_t lds = lds_for(qt);
-    if (lds > 160 * 1024) return LGEN_ERR_BAD_ARG;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)attn_prefill_tiled_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(attn_prefill_tiled_kernel<D>, dim3(B2 * n_head, (T + qt - 1) / qt), dim3(256), lds, st, q_rows, k_cache, v_cache,
-                       out_packed, mask, T, B2, MTs, n_head, hd, hdp, S8, kvs, sf, qt);
-    LGEN_CHECK_LAUNCH();
-    return 0;
+    return launch(attn_prefill_tiled_kernel<D>, dim3(B2 * n_head, (T + qt - 1) / qt), lds_for(qt), qt);
 }
 
 extern "C" int lgen_attn_prefill(const void* q_rows, const void* k_cache, const void* v_cache, void* out_packed,
                                  const unsigned char* mask, int T, int B2, int MTs, int n_head, int hd, int hdp, int S8,
                                  int kv_row_stride, int dtype, void* stream) {
     if (T < 1 || T > S8 || (long long)B2 * T > (long long)MTs * 16) return LGEN_ERR_BAD_ARG;
-    const int kvs = kv_row_stride > 0 ? kv_row_stride : hdp;
-    {
-        const int epl = dtype != LGEN_F32 ? 8 : 4;
-        if (kvs % epl || kvs < (hd + epl - 1) / epl * epl) return LGEN_ERR_BAD_ARG;
-    }
+    const int kvs = kv_row_stride > 0 ? kv_row_stride : hdp, epl = epl_of(dtype);
+    if (kvs % epl || kvs < (hd + epl - 1) / epl * epl) return LGEN_ERR_BAD_ARG;
     const float sf = sqrtf(1.0f / sqrtf((float)hd));
+    hipStream_t st = (hipStream_t)stream;
     if (dtype == LGEN_BF16 && g_prefill_mfma && (hdp == 64 || hdp == 128) && kvs % 8 == 0 && (hd & 3) == 0) {
         dim3 grid(B2 * n_head, (T + 63) / 64);
-        if (hdp == 64)
-            hipLaunchKernelGGL(attn_prefill_mfma_kernel<64>, grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)q_rows,
-                               (const uint16_t*)k_cache, (const uint16_t*)v_cache, out_packed, mask, T, B2, MTs, n_head, hd, S8, kvs, sf * sf);
-        else
-            hipLaunchKernelGGL(attn_prefill_mfma_kernel<128>, grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)q_rows,
-                               (const uint16_t*)k_cache, (const uint16_t*)v_cache, out_packed, mask, T, B2, MTs, n_head, hd, S8, kvs, sf * sf);
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, (const uint16_t*)q_rows, (const uint16_t*)k_cache,
+                               (const uint16_t*)v_cache, out_packed, mask, T, B2, MTs, n_head, hd, S8, kvs, sf * sf);
+        };
+        if (hdp == 64) launch(attn_prefill_mfma_kernel<64>); else launch(attn_prefill_mfma_kernel<128>);
         LGEN_CHECK_LAUNCH();
         return 0;
     }
-    if (T > PF_MAXT) {
-        if (dtype == LGEN_BF16)
-            return launch_attn_prefill_tiled<BF16>(q_rows, k_cache, v_cache, out_packed, mask, T, B2, MTs, n_head, hd, hdp, S8, kvs, sf,
-                                                   (hipStream_t)stream);
-        if (dtype == LGEN_F32)
-            return launch_attn_prefill_tiled<F32>(q_rows, k_cache, v_cache, out_packed, mask, T, B2, MTs, n_head, hd, hdp, S8, kvs, sf,
-                                                  (hipStream_t)stream);
-        if (dtype == LGEN_F16)
-            return launch_attn_prefill_tiled<F16>(q_rows, k_cache, v_cache, out_packed, mask, T, B2, MTs, n_head, hd, hdp, S8, kvs, sf,
-                                                  (hipStream_t)stream);
-        return LGEN_ERR_BAD_ARG;
-    }
-    const size_t lds = ((size_t)2 * T * (hd + 1) + 4 * PF_MAXT + 4 * hd) * sizeof(float);
-    if (lds > 160 * 1024) return LGEN_ERR_BAD_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == LGEN_BF16) {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void*)attn_prefill_kernel<BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return (int)e;
-        }
-        hipLaunchKernelGGL(attn_prefill_kernel<BF16>, dim3(B2 * n_head), dim3(256), lds, st, q_rows, k_cache, v_cache, out_packed, mask,
-                           T, B2, MTs, n_head, hd, hdp, S8, kvs, sf);
-    } else if (dtype == LGEN_F16) {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void*)attn_prefill_kernel<F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return (int)e;
-        }
-        hipLaunchKernelGGL(attn_prefill_kernel<F16>, dim3(B2 * n_head), dim3(256), lds, st, q_rows, k_cache, v_cache, out_packed, mask,
-                           T, B2, MTs, n_head, hd, hdp, S8, kvs, sf);
-    } else if (dtype == LGEN_F32) {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void*)attn_prefill_kernel<F32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return (int)e;
-        }
-        hipLaunchKernelGGL(attn_prefill_kernel<F32>, dim3(B2 * n_head), dim3(256), lds, st, q_rows, k_cache, v_cache, out_packed, mask,
-                           T, B2, MTs, n_head, hd, hdp, S8, kvs, sf);
-    } else {
-        return LGEN_ERR_BAD_ARG;
-    }
-    LGEN_CHECK_LAUNCH();
-    return 0;
+    return lgen_dispatch_dtype(dtype, [&](auto tag) {
+        return launch_attn_prefill<decltype(tag)>(q_rows, k_cache, v_cache, out_packed, mask, T, B2, MTs, n_head, hd, hdp, S8, kvs, sf, st);
+    });
 }

@@ -14,6 +14,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/lgen.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
@@ -322,3 +323,20 @@ static inline int lgen_cu_count() {
     return n_cu[d];
 }
 #define LGEN_CHECK_LAUNCH() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
+
+// Run-time storage code (LGEN_BF16 / LGEN_F16 / LGEN_F32) -> compile-time storage type: calls f with a value of BF16 / F16 / F32
+// as a tag and returns what f returns; an unknown code is LGEN_ERR_BAD_ARG.  The one place a launcher names the three types:
+//     return lgen_dispatch_dtype(dtype, [&](auto tag) { using D = decltype(tag); ... launch kernel<D> ...; return 0; });
+template <typename F>
+static inline int lgen_dispatch_dtype(int dtype, F&& f) {
+    switch (dtype) {
+        case LGEN_BF16: return f(BF16{});
+        case LGEN_F16: return f(F16{});
+        case LGEN_F32: return f(F32{});
+        default: return LGEN_ERR_BAD_ARG;
+    }
+}
+// D::KC / D::EPL for argument checks that come before the dispatch (any code but LGEN_F32 counts as 16-bit storage there; the
+// dispatch refuses the unknown ones)
+static inline int kc_of(int dtype) { return dtype == LGEN_F32 ? F32::KC : BF16::KC; }
+static inline int epl_of(int dtype) { return dtype == LGEN_F32 ? F32::EPL : BF16::EPL; }

@@ -514,16 +514,11 @@ static int sample_impl(const void* logits, const float* noise, long long noise_s
         if (e2 != hipSuccess) return (int)e2;
         attr_set_mask |= 1ull << dev_i;
     }
-    if (dtype == LGEN_BF16)
-        hipLaunchKernelGGL(sample_kernel<BF16>, dim3(B), dim3(SMP_THREADS), lds, st, a);
-    else if (dtype == LGEN_F32)
-        hipLaunchKernelGGL(sample_kernel<F32>, dim3(B), dim3(SMP_THREADS), lds, st, a);
-    else if (dtype == LGEN_F16)
-        hipLaunchKernelGGL(sample_kernel<F16>, dim3(B), dim3(SMP_THREADS), lds, st, a);
-    else
-        return LGEN_ERR_BAD_ARG;
-    LGEN_CHECK_LAUNCH();
-    return 0;
+    return lgen_dispatch_dtype(dtype, [&](auto tag) {
+        hipLaunchKernelGGL(sample_kernel<decltype(tag)>, dim3(B), dim3(SMP_THREADS), lds, st, a);
+        LGEN_CHECK_LAUNCH();
+        return 0;
+    });
 }
 
 extern "C" int lgen_sample(const void* logits, const float* noise, long long noise_step_stride, int* cur_tok, int* seq,

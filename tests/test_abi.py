@@ -224,6 +224,17 @@ def test_pinned_tile_schedules_are_shapes_the_library_takes(lib):
         assert (rc not in (-1, -2)) == want_ok, (dtype, stride, rc)
 
 
+def test_embed_launchers_refuse_rows_wider_than_the_statistics_stride(lib):
+    """ssq_out rows hold LGEN_SSQ_STRIDE partials (one per 16 columns): with statistics requested, d / 16 beyond that is refused by
+    lgen_embed_rows exactly as by lgen_embed_pack (it used to launch and write past the row).  Only the refused shape is called:
+    the pointers are dummies."""
+    from llamagen_amd import _lib as L
+    d = 16 * (L.SSQ_STRIDE + 2)            # 4128: a multiple of 32, 258 partials
+    for dtype in (L.BF16, L.F16, L.F32):
+        assert lib.lgen_embed_rows(8, 8, 8, 8, 8, 8, 8, 16, 1, d, 50, 10, dtype, 0) == L.ERR_BAD_ARG, dtype
+        assert lib.lgen_embed_pack(8, 8, 8, 8, 0, 16, 1, d, 50, dtype, 0) == L.ERR_BAD_ARG, dtype
+
+
 def test_hot_kernels_have_no_register_spills():
     """The build leaves the compiler's per-kernel resource report next to every object
     (llamagen_amd/csrc/*.usage, -Rpass-analysis=kernel-resource-usage).  Every kernel of the library must be free
