@@ -13,7 +13,8 @@
  * LGEN_GEMM_STEADY / LGEN_TILE_ABLATE environment variables (read at launch = capture time; bit-identical results / timing
  * ablations).  ABI v8 = v7 + a K/V row stride that may be smaller than the lane group hdp (lgen_gemm_qkv_rope); ABI v9 = v8 minus
  * lgen_conv_wino (the Winograd experiment of round 5 left the product library: tools/experiments/conv_wino/); ABI v10 = v9 +
- * lgen_ssq_group4 (row statistics pre-grouped for the fused-norm consumers) and key-row stride checks in the prefill entry points.  Each entry point
+ * lgen_ssq_group4 (row statistics pre-grouped for the fused-norm consumers) and key-row stride checks in the prefill entry points;
+ * v10 + lgen_sample_rows_params is additive (a new symbol, nothing else changes), so the version number stays 10.  Each entry point
  * cites the reference op sequence it replaces (paths relative to the reference repository root).
  *
  * Fragment-packed layouts ("chunk" = 1 KiB = [16 rows][KC k] in MFMA operand order, lane =
@@ -200,6 +201,24 @@ int lgen_attn_decode_rows(const void* q, const void* k_cache, const void* v_cach
 int lgen_sample_rows(const void* logits, const float* noise, int* cur_tok, int* seq, int* row_step, int* row_pos, int max_steps,
                      int B, int V, int seq_stride, int use_cfg, float cfg_scale, int cfg_interval, float temperature, int top_k,
                      float top_p, int greedy, int dtype, void* stream);
+
+/* Sampling values of one slot (the SamplingParams fields serve/sampler.py:65-83 consumes, plus the guidance pair): one 32-byte
+ * record per slot, read once per workgroup at a workgroup-uniform address. */
+typedef struct { float cfg_scale, temperature, top_p; int cfg_interval, top_k, greedy; int reserved[2]; } lgen_slot_sampling;
+
+/* lgen_sample_rows with PER-SLOT sampling values (serve/sampler.py:54-58,65-83,106-108; one SamplingParams per prompt,
+ * serve/llm.py:141-210): slot b samples with params[b] ([B] records, device) instead of six batch-wide scalars.
+ *   guidance: mixed only if use_cfg (the batch has unconditional rows B + b) AND params[b].cfg_scale > 1, under the slot's own
+ *     cfg_interval at its own row_step[b]; a slot with cfg_scale <= 1 in a guided batch samples its conditional logits unchanged
+ *     (the reference's cfg_scale <= 1.0 branch, not uncond + (cond - uncond) * 1); cur_tok[B+b] and row_pos[B+b] are written and
+ *     advanced all the same, so its unconditional row stays a valid, finite row;
+ *   temperature, top_k, top_p, greedy: per slot; a greedy slot reads no noise.  CALLER'S CONTRACT: noise may be null only if every
+ *     live slot (row_step[b] < max_steps) is greedy -- the launcher cannot see device values and does not check it;
+ *   records that all hold the same values give the tokens of lgen_sample_rows with those scalars, bit for bit.
+ * LGEN_ERR_BAD_ARG before any launch: params, row_step or row_pos null, max_steps < 1. */
+int lgen_sample_rows_params(const void* logits, const float* noise, int* cur_tok, int* seq, int* row_step, int* row_pos,
+                            int max_steps, int B, int V, int seq_stride, int use_cfg, const lgen_slot_sampling* params, int dtype,
+                            void* stream);
 
 /* ---- VQ-VAE tokenizer (tokenizer/tokenizer_image/vq_model.py), fp32 NHWC activations ------------- */
 

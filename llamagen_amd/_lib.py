@@ -52,6 +52,8 @@ SIGNATURES = {
     "lgen_gemm_qkv_rope_rows": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _F, _I, _P],
     "lgen_attn_decode_rows": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "lgen_sample_rows": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _F, _I, _F, _I, _I, _P],
+    # per-slot SamplingParams records in place of the six scalars (serve/sampler.py:54-58,65-83,106-108)
+    "lgen_sample_rows_params": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P],
     "lgen_vq_codebook_prep": [_P, _P, _P, _I, _I, _I, _P],
     "lgen_vq_lookup_pqconv": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "lgen_vq_argmin": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
@@ -64,6 +66,13 @@ SIGNATURES = {
     "lgen_gn_finalize": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P],
     "lgen_conv_igemm": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _c.c_longlong, _F, _P],
 }
+
+
+class SlotSampling(ctypes.Structure):
+    """lgen_slot_sampling (include/lgen.h): the 32-byte per-slot record lgen_sample_rows_params reads."""
+    _fields_ = [("cfg_scale", _F), ("temperature", _F), ("top_p", _F), ("cfg_interval", _I), ("top_k", _I), ("greedy", _I),
+                ("reserved", _I * 2)]
+
 
 _lib = None
 

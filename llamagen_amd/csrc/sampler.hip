@@ -38,6 +38,8 @@ struct SampleArgs {
     int* row_step;         // [B]
     int* row_pos;          // [2B or B]
     int max_steps;
+    // per-request sampling (serve/sampler.py:65-83; null otherwise): slot b takes the six values above from params[b] instead
+    const lgen_slot_sampling* params;  // [B]
 };
 
 // Ownership: thread t owns the 8 consecutive vocabulary entries of slot s at i = (s*1024 + t)*8
@@ -135,8 +137,15 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) {
     const int b = blockIdx.x, V = a.V, B = a.B;
     const int step = a.row_step ? a.row_step[b] : a.state[1];
     if (a.row_step && step >= a.max_steps) return;  // empty / finished slot (uniform over the workgroup)
+    bool guided = a.use_cfg;
+    if (a.params) {  // the slot's own record: one 32-byte load at an address that depends on blockIdx.x only, so every branch on
+        const lgen_slot_sampling r = a.params[b];  // these values stays uniform over the workgroup
+        a.cfg_scale = r.cfg_scale; a.temperature = r.temperature; a.top_p = r.top_p;
+        a.cfg_interval = r.cfg_interval; a.top_k = r.top_k; a.greedy = r.greedy;
+        guided = guided && r.cfg_scale > 1.0f;  // serve/sampler.py:54-58: an unguided request keeps its conditional logits as they are
+    }
     // generate.py:113-114: decode iteration i = step-1 drops guidance once i > cfg_interval
-    const bool mix = a.use_cfg && !(step > 0 && a.cfg_interval > -1 && (step - 1) > a.cfg_interval);
+    const bool mix = guided && !(step > 0 && a.cfg_interval > -1 && (step - 1) > a.cfg_interval);
     const float tdiv = fmaxf(a.temperature, 1e-5f);
 
     // 0. request everything this thread will ever read from HBM
@@ -493,11 +502,11 @@ __global__ void advance_state_kernel(int* state) {
 static int sample_impl(const void* logits, const float* noise, long long noise_step_stride, int* cur_tok, int* seq,
                        const int* state, int B, int V, int seq_stride, int use_cfg, float cfg_scale,
                        int cfg_interval, float temperature, int top_k, float top_p, int greedy, int dtype,
-                       int* row_step, int* row_pos, int max_steps, void* stream) {
+                       int* row_step, int* row_pos, int max_steps, const lgen_slot_sampling* params, void* stream) {
     if (V > SMP_MAXV || V < 8 || (V & 7) || B < 1) return LGEN_ERR_BAD_ARG;
-    if (!greedy && !noise) return LGEN_ERR_BAD_ARG;
+    if (!params && !greedy && !noise) return LGEN_ERR_BAD_ARG;  // with records `greedy` lives on the device: the caller's contract
     SampleArgs a{logits, noise, noise_step_stride, cur_tok, seq, state, B, V, seq_stride, use_cfg, cfg_scale,
-                 temperature, top_p, cfg_interval, top_k, greedy, row_step, row_pos, max_steps};
+                 temperature, top_p, cfg_interval, top_k, greedy, row_step, row_pos, max_steps, params};
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = (size_t)SMP_MAXV * sizeof(float);
     static unsigned long long attr_set_mask = 0;   // per device
@@ -526,7 +535,7 @@ extern "C" int lgen_sample(const void* logits, const float* noise, long long noi
                            int cfg_interval, float temperature, int top_k, float top_p, int greedy, int dtype,
                            void* stream) {
     return sample_impl(logits, noise, noise_step_stride, cur_tok, seq, state, B, V, seq_stride, use_cfg, cfg_scale, cfg_interval,
-                       temperature, top_k, top_p, greedy, dtype, nullptr, nullptr, 0, stream);
+                       temperature, top_k, top_p, greedy, dtype, nullptr, nullptr, 0, nullptr, stream);
 }
 
 // Continuous batching form (autoregressive/serve/sampler.py:54-58,106-108: paired cond / uncond sequences, every request at its
@@ -537,7 +546,20 @@ extern "C" int lgen_sample_rows(const void* logits, const float* noise, int* cur
                                 float temperature, int top_k, float top_p, int greedy, int dtype, void* stream) {
     if (!row_step || !row_pos || max_steps < 1) return LGEN_ERR_BAD_ARG;
     return sample_impl(logits, noise, 0, cur_tok, seq, nullptr, B, V, seq_stride, use_cfg, cfg_scale, cfg_interval, temperature,
-                       top_k, top_p, greedy, dtype, row_step, row_pos, max_steps, stream);
+                       top_k, top_p, greedy, dtype, row_step, row_pos, max_steps, nullptr, stream);
+}
+
+// Per-request form (serve/sampler.py:54-58,65-83,106-108: one SamplingParams per sequence): lgen_sample_rows with the six sampling
+// values of slot b read from params[b].  Guidance needs both the batch's unconditional rows (use_cfg) and the slot's own
+// cfg_scale > 1; an unguided slot of a guided batch samples its conditional logits unchanged and still feeds its unconditional row
+// the token.  A greedy slot reads no noise; noise may be null only when every live slot is greedy (the caller's contract: the
+// launcher cannot see device values).
+extern "C" int lgen_sample_rows_params(const void* logits, const float* noise, int* cur_tok, int* seq, int* row_step, int* row_pos,
+                                       int max_steps, int B, int V, int seq_stride, int use_cfg, const lgen_slot_sampling* params,
+                                       int dtype, void* stream) {
+    if (!params || !row_step || !row_pos || max_steps < 1) return LGEN_ERR_BAD_ARG;
+    return sample_impl(logits, noise, 0, cur_tok, seq, nullptr, B, V, seq_stride, use_cfg, 1.0f, -1, 1.0f, 0, 1.0f, 0, dtype, row_step,
+                       row_pos, max_steps, params, stream);
 }
 
 extern "C" int lgen_advance_state(int* state, void* stream) {

@@ -25,14 +25,26 @@ request -- its K/V rows, token, position, class id and mask rows, and (when its 
 -- into the new bucket's rows with stream-ordered device copies, so a lightly loaded server replays a 32-row graph instead of a
 128-row one and still never recomputes a prefix.
 
-Every request produces exactly the tokens a batch-of-one `generate()` would with the same noise: rows are independent
-through every kernel (tests/test_gpu_serve.py holds that to the oracle, token for token, in fp32).
+Per-request sampling (serve/llm.py:141-210 one SamplingParams per prompt, serve/sampler.py:65-83 per-sequence temperature /
+top-k / top-p, serve/model_runner.py:620-645 per-request seeds): `submit(..., sampling=SamplingParams(...))` overrides the
+constructor's values -- which are the DEFAULTS -- for that request.  The values travel as one 32-byte record per slot in a
+slot-indexed device tensor that the sampler kernel reads (lgen_sample_rows_params).  Whether the step batch has unconditional rows
+is fixed by the constructor (it fixes the row layout and the captured graphs): an unguided request in a guided batcher samples its
+conditional logits unchanged and still pays for its unconditional row.
+
+Every request produces exactly the tokens a batch-of-one `generate()` would with the same noise and sampling values: rows are
+independent through every kernel (tests/test_gpu_serve.py and tests/test_gpu_serve_params.py hold that to the oracle, token for
+token, in fp32).
 """
 from __future__ import annotations
 
 import collections
+import ctypes
+import dataclasses
+import math
 from typing import Dict, List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -66,6 +78,41 @@ def plan_moves(active: Sequence[bool], new_slots: int):
         raise ValueError(f"{len(run)} running requests do not fit {new_slots} slots")
     free = [t for t in range(new_slots) if not (t < len(active) and active[t])]
     return [(s, s) if s < new_slots else (s, free.pop(0)) for s in run]
+
+
+@dataclasses.dataclass(frozen=True)
+class SamplingParams:
+    """Sampling values of one request (the fields of the vLLM fork's SamplingParams that serve/sampler.py:65-83 consumes, plus the
+    guidance pair of serve/sampler.py:54-58 and the per-request seed of serve/model_runner.py:620-645)."""
+    cfg_scale: float = 1.0
+    cfg_interval: int = -1
+    temperature: float = 1.0
+    top_k: int = 0
+    top_p: float = 1.0
+    sample_logits: bool = True
+    seed: Optional[int] = None
+
+    def __post_init__(self):
+        for name in ("cfg_scale", "temperature", "top_p"):
+            if not math.isfinite(float(getattr(self, name))):
+                raise ValueError(f"{name} must be finite, got {getattr(self, name)}")
+        if not 0.0 < float(self.top_p) <= 1.0:
+            raise ValueError(f"top_p must lie in (0, 1], got {self.top_p}")
+        if int(self.top_k) < 0:
+            raise ValueError(f"top_k must be >= 0 (0 = off), got {self.top_k}")
+        if int(self.top_k) != self.top_k or int(self.cfg_interval) != self.cfg_interval:
+            raise ValueError("top_k and cfg_interval are integers")
+
+
+def pack_sampling(sp: SamplingParams) -> np.ndarray:
+    """The 32-byte device record of one slot (lgen_slot_sampling, include/lgen.h) as 8 int32 words: three floats (cfg_scale,
+    temperature, top_p), three ints (cfg_interval, top_k, greedy), two reserved words.  `seed` is host-side only."""
+    rec = L.SlotSampling(float(sp.cfg_scale), float(sp.temperature), float(sp.top_p), int(sp.cfg_interval), int(sp.top_k),
+                         0 if sp.sample_logits else 1)
+    return np.frombuffer(bytes(rec), dtype=np.int32).copy()
+
+
+RECORD_WORDS = ctypes.sizeof(L.SlotSampling) // 4
 
 
 class _Bucket:
@@ -113,8 +160,11 @@ class ContinuousBatcher:
         self.row_step = torch.full((slots,), max_new_tokens, dtype=torch.int32, device=dev)  # >= N: empty slot
         self.noise = torch.empty(slots, max_new_tokens, self.V, dtype=torch.float32, device=dev) if sample_logits else None
         self.seq = torch.zeros(slots, max_new_tokens, dtype=torch.int32, device=dev)
-        self.sp = dict(cfg_scale=float(cfg_scale), cfg_interval=int(cfg_interval), temperature=float(temperature), top_k=int(top_k),
-                       top_p=float(top_p), greedy=0 if sample_logits else 1)
+        # the constructor's sampling values: what a request that brings no SamplingParams gets
+        self.defaults = SamplingParams(cfg_scale=float(cfg_scale), cfg_interval=int(cfg_interval), temperature=float(temperature),
+                                       top_k=int(top_k), top_p=float(top_p), sample_logits=bool(sample_logits))
+        self.params = torch.zeros(slots, RECORD_WORDS, dtype=torch.int32, device=dev)  # lgen_slot_sampling per slot
+        self._req_sampling: Dict[int, SamplingParams] = {}   # queued requests that brought their own values
         self._pe = None             # t2i: the private prefill engine (built on the first caption request)
         self._queue = collections.deque()
         self._slot_req: List[Optional[int]] = [None] * slots
@@ -168,6 +218,8 @@ class ContinuousBatcher:
                 if self.noise is not None:
                     self.noise[t].copy_(self.noise[s])
                 self.seq[t].copy_(self.seq[s])
+                if getattr(self, "params", None) is not None:
+                    self.params[t].copy_(self.params[s])
                 self.row_step[t:t + 1].copy_(self.row_step[s:s + 1])
                 self.row_step[s] = self.N
                 self._slot_req[t], self._slot_left[t] = self._slot_req[s], self._slot_left[s]
@@ -178,10 +230,20 @@ class ContinuousBatcher:
         self.switches += 1
 
     # ---- requests ---------------------------------------------------------------------------------------------------
-    def submit(self, class_label, noise: Optional[torch.Tensor] = None, emb_mask: Optional[torch.Tensor] = None) -> int:
+    def submit(self, class_label, noise: Optional[torch.Tensor] = None, emb_mask: Optional[torch.Tensor] = None,
+               sampling: Optional[SamplingParams] = None) -> int:
         """Queue one image request; `noise` (optional, [N, V] fp32 Exp(1) draws) replaces the default generator's draw.
         c2i: `class_label` is the class id.  t2i: `class_label` is the caption embedding [T, caption_dim] (left-padded and already
-        multiplied by its mask, sample_t2i.py:95-108) and `emb_mask` its [T] validity mask."""
+        multiplied by its mask, sample_t2i.py:95-108) and `emb_mask` its [T] validity mask.
+        `sampling` (serve/llm.py:141-210) replaces the constructor's sampling values for this request; with a `seed` and no `noise`
+        the request's Exp(1) block comes from a generator of its own, so its tokens do not depend on slot, arrival or neighbours."""
+        if sampling is not None:
+            if not isinstance(sampling, SamplingParams):
+                raise TypeError("sampling must be a llamagen_amd.serve.SamplingParams")
+            if sampling.cfg_scale > 1.0 and not self.use_cfg:
+                raise ValueError("cfg_scale > 1 needs a batcher built with cfg_scale > 1 (the step batch has no unconditional rows)")
+            if sampling.sample_logits and self.noise is None:
+                raise ValueError("sample_logits=True needs a batcher built with sample_logits=True (a greedy batcher has no noise buffer)")
         if self.t2i:
             cap = class_label
             if not torch.is_tensor(cap) or cap.dim() != 2 or cap.shape[0] != self.T:
@@ -200,18 +262,37 @@ class ContinuousBatcher:
                 raise ValueError(f"noise must be [{self.N}, {self.V}] fp32 Exp(1) draws, got {tuple(noise.shape)}")
         rid = self._next_id
         self._next_id += 1
+        if sampling is not None:   # a side table, not a fourth queue field: the queue entries stay (rid, label, noise)
+            self.__dict__.setdefault("_req_sampling", {})[rid] = sampling
         self._queue.append((rid, label, noise))
         return rid
 
+    def _sampling_of(self, rid: int) -> Optional[SamplingParams]:
+        """The request's own values (taken out of the side table), else the constructor's."""
+        own = getattr(self, "_req_sampling", None)
+        sp = own.pop(rid, None) if own else None
+        return sp if sp is not None else getattr(self, "defaults", None)
+
     def _load(self, b: int, rid: int, label, noise):
-        """Slot b <- a fresh request: position / step 0, its class label, its noise block (stream-ordered scalar writes)."""
+        """Slot b <- a fresh request: position / step 0, its class label, its noise block and its sampling record (stream-ordered
+        writes, no sync)."""
+        sp = self._sampling_of(rid)
+        if sp is not None and getattr(self, "params", None) is not None:
+            rec = torch.from_numpy(pack_sampling(sp))
+            if self.params.is_cuda:   # pinned staging: the copy is enqueued, the host does not wait for it
+                rec = rec.pin_memory()
+            self.params[b].copy_(rec, non_blocking=True)
         if self.noise is not None:
             if noise is not None:
                 self.noise[b].copy_(noise.to(self.dev))
+            elif sp is not None and not sp.sample_logits:
+                pass  # a greedy request reads no noise: nothing drawn, the other requests' draws stay where they were
+            elif sp is not None and sp.seed is not None:   # serve/model_runner.py:620-645: a generator per seeded request
+                self.noise[b].exponential_(1.0, generator=torch.Generator(device=self.dev).manual_seed(int(sp.seed)))
             else:
                 self.noise[b].exponential_(1.0)
         if self.t2i:
-            self._load_caption(b, *label)
+            self._load_caption(b, *label, sp=sp)
             self._slot_req[b], self._slot_left[b] = rid, self.N - 1   # the first token was sampled by the prefill
             return
         self.row_pos[b] = 0
@@ -221,10 +302,12 @@ class ContinuousBatcher:
             self.row_pos[self.B + b] = 0
         self._slot_req[b], self._slot_left[b] = rid, self.N
 
-    def _load_caption(self, b: int, cap: torch.Tensor, emb_mask):
+    def _load_caption(self, b: int, cap: torch.Tensor, emb_mask, sp: Optional[SamplingParams] = None):
         """Per-request prefill of a text-conditional request (generate.py:128-170 for ONE image): caption (+ null caption with
         CFG) through the CaptionEmbedder and all T prefix positions of every layer on the private engine, first image token sampled
-        from the slot's noise block, then K/V slots 0..T-1, mask rows, token and counters move into slot b of the step batch."""
+        from the slot's noise block with the REQUEST's sampling values (an unguided request of a guided batcher samples its
+        conditional row alone), then K/V slots 0..T-1, mask rows, token and counters move into slot b of the step batch."""
+        sp = sp if sp is not None else self.defaults
         e, T, dev = self.eng, self.T, self.dev
         rows = 2 if self.use_cfg else 1
         if self._pe is None:
@@ -243,11 +326,10 @@ class ContinuousBatcher:
         pe.state[0] = T - 1
         pe.state[1] = 0
         pe._final_logits()
-        sp = dict(use_cfg=self.use_cfg, cfg_scale=self.sp["cfg_scale"], cfg_interval=self.sp["cfg_interval"],
-                  temperature=self.sp["temperature"], top_k=self.sp["top_k"], top_p=self.sp["top_p"],
-                  sample_logits=not self.sp["greedy"])
+        first = dict(use_cfg=self.use_cfg and sp.cfg_scale > 1.0, cfg_scale=sp.cfg_scale, cfg_interval=sp.cfg_interval,
+                     temperature=sp.temperature, top_k=sp.top_k, top_p=sp.top_p, sample_logits=sp.sample_logits)
         pe.noise = self.noise[b].view(self.N, 1, self.V) if self.noise is not None else None
-        pe._sample(1, sp)
+        pe._sample(1, first)   # writes cur_tok[0]; both step-batch rows take it below
         for src, dst in ((0, b),) + (((1, self.B + b),) if self.use_cfg else ()):
             e.k_cache[:, dst, :, :T].copy_(pe.k_cache[:, src, :, :T])
             e.v_cache[:, dst, :, :T].copy_(pe.v_cache[:, src, :, :T])
@@ -259,17 +341,17 @@ class ContinuousBatcher:
 
     # ---- one step of the whole slot batch -------------------------------------------------------------------------------
     def _step(self):
-        e, lib, sp = self.eng, self.eng.lib, self.sp
+        e, lib = self.eng, self.eng.lib
         cls = e.tok_emb if self.t2i else e.cls_emb   # t2i rows never sit at position 0 (their prefix is prefilled): table unused
         L.check(lib.lgen_embed_rows(L.ptr(e.tok_emb), L.ptr(cls), L.ptr(e.cur_tok), L.ptr(self.cond), L.ptr(self.row_pos),
                                     L.ptr(e.hp), L.ptr(e.ssq) if e.fuse_norm else 0, self.B2, e.MTs, e.d, e.tok_emb.shape[0],
                                     cls.shape[0], e.dt, L.stream()), "embed_rows")
         e.ssq_parts = e.d // 16
         e._layers_and_logits()
-        L.check(lib.lgen_sample_rows(L.ptr(e.logits), L.ptr(self.noise), L.ptr(e.cur_tok), L.ptr(self.seq), L.ptr(self.row_step),
-                                     L.ptr(self.row_pos), self.N, self.B, e.V, self.N, 1 if self.use_cfg else 0, sp["cfg_scale"],
-                                     sp["cfg_interval"], sp["temperature"], sp["top_k"], sp["top_p"], sp["greedy"], e.dt, L.stream()),
-                "sample_rows")
+        # noise is null only in a batcher built greedy, and submit() lets no sampled request into one (the kernel's contract)
+        L.check(lib.lgen_sample_rows_params(L.ptr(e.logits), L.ptr(self.noise), L.ptr(e.cur_tok), L.ptr(self.seq), L.ptr(self.row_step),
+                                            L.ptr(self.row_pos), self.N, self.B, e.V, self.N, 1 if self.use_cfg else 0,
+                                            L.ptr(self.params), e.dt, L.stream()), "sample_rows_params")
 
     def run(self, use_graph: bool = True) -> Dict[int, torch.Tensor]:
         """Drain the queue; returns {request id: int32 [N] token ids} (device tensors, enqueued on the current stream)."""
