@@ -46,8 +46,24 @@ def build_parser():
     p.add_argument("--top-k", type=int, default=2000, help="top-k value to sample with")
     p.add_argument("--temperature", type=float, default=1.0, help="temperature value to sample with")
     p.add_argument("--top-p", type=float, default=1.0, help="top-p value to sample with")
+    p.add_argument("--best-of", type=int, default=1, help="draw K candidates per class id and keep the likeliest (continuous batcher)")
     p.add_argument("--out", type=str, default=None, help="image grid path (default sample_<gpt-type>.png)")
     return p
+
+
+def best_of_sample(gpt_model, c_indices, n_tokens, args):
+    """--best-of K: K candidates per class id through the continuous batcher (serve/llm.py `best_of`), the one with the largest
+    cumulative log-probability kept.  Candidate j of image i draws its noise from seed args.seed + i * K + j."""
+    from llamagen_amd.serve import ContinuousBatcher, SamplingParams
+    k = int(args.best_of)
+    skw = dict(cfg_scale=args.cfg_scale, cfg_interval=int(args.cfg_interval), temperature=args.temperature, top_k=args.top_k,
+               top_p=args.top_p)
+    cb = ContinuousBatcher(gpt_model, max(k, min(len(c_indices) * k, 64)), n_tokens, sample_logits=True, **skw)
+    rids = [cb.submit(int(c), sampling=SamplingParams(seed=args.seed + i * k, best_of=k, **skw)) for i, c in enumerate(c_indices.tolist())]
+    out = cb.run(return_outputs=True)
+    for i, r in enumerate(rids):
+        print(f"image {i}: kept the likeliest of {k} candidates, log-likelihood {float(out[r].cumulative_logprob):.1f}")
+    return torch.stack([out[r].token_ids for r in rids])
 
 
 def main(args, class_labels=None):
@@ -75,8 +91,11 @@ def main(args, class_labels=None):
     qzshape = [len(c_indices), args.codebook_embed_dim, latent_size, latent_size]
 
     t1 = time.time()
-    index_sample = generate(gpt_model, c_indices, latent_size ** 2, cfg_scale=args.cfg_scale, cfg_interval=int(args.cfg_interval),
-                            temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, sample_logits=True)
+    if getattr(args, "best_of", 1) > 1:
+        index_sample = best_of_sample(gpt_model, c_indices, latent_size ** 2, args)
+    else:
+        index_sample = generate(gpt_model, c_indices, latent_size ** 2, cfg_scale=args.cfg_scale, cfg_interval=int(args.cfg_interval),
+                                temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, sample_logits=True)
     torch.cuda.synchronize()  # the reference's bracket has no device sync; this one does
     sampling_time = time.time() - t1
     print(f"gpt sampling takes about {sampling_time:.2f} seconds.")

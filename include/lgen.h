@@ -14,7 +14,8 @@
  * ablations).  ABI v8 = v7 + a K/V row stride that may be smaller than the lane group hdp (lgen_gemm_qkv_rope); ABI v9 = v8 minus
  * lgen_conv_wino (the Winograd experiment of round 5 left the product library: tools/experiments/conv_wino/); ABI v10 = v9 +
  * lgen_ssq_group4 (row statistics pre-grouped for the fused-norm consumers) and key-row stride checks in the prefill entry points;
- * v10 + lgen_sample_rows_params is additive (a new symbol, nothing else changes), so the version number stays 10.  Each entry point
+ * v10 + lgen_sample_rows_params is additive (a new symbol, nothing else changes), so the version number stays 10; so are
+ * lgen_sample_logprob, lgen_sample_rows_params_logprob and lgen_logprob_rows (per-token log-probabilities).  Each entry point
  * cites the reference op sequence it replaces (paths relative to the reference repository root).
  *
  * Fragment-packed layouts ("chunk" = 1 KiB = [16 rows][KC k] in MFMA operand order, lane =
@@ -173,6 +174,27 @@ int lgen_sample(const void* logits, const float* noise, long long noise_step_str
                 const int* state, int B, int V, int seq_stride, int use_cfg, float cfg_scale, int cfg_interval,
                 float temperature, int top_k, float top_p, int greedy, int dtype, void* stream);
 
+/* lgen_sample + the log-probability of the token it sampled (serve/sampler.py:88-93: log_softmax of the FINAL sampling
+ * distribution -- after the CFG mix, / max(temperature, 1e-5), the top-k threshold and the top-p nucleus with its renormalised
+ * sum; :119-123 _get_logprobs: the sampled token's entry).  logprob_out fp32, indexed like seq: logprob_out[b * seq_stride + step]
+ * = (l[token] - max l) - log(sum of exp over the kept set); for a greedy call the probability the argmax ranks.  Tokens, cur_tok
+ * and seq are those of lgen_sample bit for bit.  A row whose ratios are all NaN keeps token 0; its log-probability is unspecified.
+ * LGEN_ERR_BAD_ARG: logprob_out null. */
+int lgen_sample_logprob(const void* logits, const float* noise, long long noise_step_stride, int* cur_tok, int* seq,
+                        const int* state, int B, int V, int seq_stride, int use_cfg, float cfg_scale, int cfg_interval,
+                        float temperature, int top_k, float top_p, int greedy, int dtype, float* logprob_out, void* stream);
+
+/* Scoring of GIVEN tokens (serve/sampler.py:88-93,119-123 without the filters; the per-token term of the cross-entropy of
+ * gpt.py:373-380): out[r] = log_softmax(mix(row r) / max(temperature, 1e-5))[targets[r]], fp32, for r < R.
+ *   logits [>= R (+ pair_offset)][V] storage dtype, row-major (what the EPI_ROWS lm_head writes); targets [R] int32; out [R] fp32;
+ *   mix = uncond + (cond - uncond) * cfg_scale with uncond = row r + pair_offset when pair_offset > 0 and cfg_scale > 1
+ *     (serve/sampler.py:54-58), else the row itself; no top-k / top-p (a filtered target would be -inf);
+ *   targets[r] < 0: the row is not read and out[r] = 0; targets[r] >= V is the caller's error.
+ * One pass, fp32 math, nothing of width V is stored.  LGEN_ERR_BAD_ARG: V < 8, V % 8 != 0, V > 16384, R < 1, pair_offset < 0, a
+ * null pointer. */
+int lgen_logprob_rows(const void* logits, const int* targets, float* out, int R, int V, int pair_offset, float cfg_scale,
+                      float temperature, int dtype, void* stream);
+
 int lgen_advance_state(int* state, void* stream);
 
 /* ---- continuous batching (autoregressive/serve/: the vLLM fork's token-level scheduling -- every row of the step batch is its
@@ -219,6 +241,14 @@ typedef struct { float cfg_scale, temperature, top_p; int cfg_interval, top_k, g
 int lgen_sample_rows_params(const void* logits, const float* noise, int* cur_tok, int* seq, int* row_step, int* row_pos,
                             int max_steps, int B, int V, int seq_stride, int use_cfg, const lgen_slot_sampling* params, int dtype,
                             void* stream);
+
+/* lgen_sample_rows_params + the sampled token's log-probability under the SLOT's own final sampling distribution (see
+ * lgen_sample_logprob; serve/sampler.py:88-93,119-123): logprob_out [B][seq_stride] fp32, entry (b, row_step[b]) like seq.  A
+ * skipped slot (row_step[b] >= max_steps) writes nothing.  Tokens and counters are those of lgen_sample_rows_params bit for bit.
+ * LGEN_ERR_BAD_ARG additionally: logprob_out null. */
+int lgen_sample_rows_params_logprob(const void* logits, const float* noise, int* cur_tok, int* seq, int* row_step, int* row_pos,
+                                    int max_steps, int B, int V, int seq_stride, int use_cfg, const lgen_slot_sampling* params,
+                                    int dtype, float* logprob_out, void* stream);
 
 /* ---- VQ-VAE tokenizer (tokenizer/tokenizer_image/vq_model.py), fp32 NHWC activations ------------- */
 

@@ -8,6 +8,6 @@ declared in include/lgen.h; importing the package does not need a GPU, running i
 """
 from .gpt import GPT_models, ModelArgs, Transformer  # noqa: F401
 from .vq_model import VQ_models, VQModel  # noqa: F401
-from .generate import generate  # noqa: F401
+from .generate import generate, score  # noqa: F401
 
-__all__ = ["GPT_models", "VQ_models", "generate", "Transformer", "VQModel", "ModelArgs"]
+__all__ = ["GPT_models", "VQ_models", "generate", "score", "Transformer", "VQModel", "ModelArgs"]

@@ -54,6 +54,10 @@ SIGNATURES = {
     "lgen_sample_rows": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _F, _I, _F, _I, _I, _P],
     # per-slot SamplingParams records in place of the six scalars (serve/sampler.py:54-58,65-83,106-108)
     "lgen_sample_rows_params": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P],
+    # the same two samplers + the sampled token's log-probability (serve/sampler.py:88-93,119-123), and scoring of given tokens
+    "lgen_sample_logprob": [_P, _P, _c.c_longlong, _P, _P, _P, _I, _I, _I, _I, _F, _I, _F, _I, _F, _I, _I, _P, _P],
+    "lgen_sample_rows_params_logprob": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P],
+    "lgen_logprob_rows": [_P, _P, _P, _I, _I, _I, _F, _F, _I, _P],
     "lgen_vq_codebook_prep": [_P, _P, _P, _I, _I, _I, _P],
     "lgen_vq_lookup_pqconv": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "lgen_vq_argmin": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],

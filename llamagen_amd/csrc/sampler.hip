@@ -40,6 +40,9 @@ struct SampleArgs {
     int max_steps;
     // per-request sampling (serve/sampler.py:65-83; null otherwise): slot b takes the six values above from params[b] instead
     const lgen_slot_sampling* params;  // [B]
+    // log-probability of the sampled token under the final sampling distribution (serve/sampler.py:88-93,119-123; null: not
+    // wanted): logprob[b * seq_stride + step], the slot `seq` writes
+    float* logprob;
 };
 
 // Ownership: thread t owns the 8 consecutive vocabulary entries of slot s at i = (s*1024 + t)*8
@@ -490,8 +493,27 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) {
             a.row_pos[b] += 1;
             if (a.use_cfg) a.row_pos[B + b] += 1;
         }
+        if (a.logprob) sel[0] = (unsigned)bi;
+    }
+    // log p(token) = (l - rmax) - log(tot), from the scaled logit itself (not log(ex / tot): ex underflows long before l - rmax
+    // does).  The owner of the chosen entry still holds its l in registers; the whole block hangs off a workgroup-uniform pointer
+    // test, so a launch without the buffer runs none of it.
+    if (a.logprob) {
+        __syncthreads();
+        const int bi = (int)sel[0];
+        if (tid == ((bi >> 3) & (SMP_THREADS - 1))) {
+            const int cs = bi >> 13, ce = bi & 7;  // bi = (s * SMP_THREADS + tid) * 8 + e
+            float lc = 0.f;
+#pragma unroll
+            for (int s = 0; s < SMP_NS; ++s)
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                    if (s == cs && e == ce) lc = l[s][e];
+            a.logprob[(size_t)b * a.seq_stride + step] = (lc - rmax) - logf(tot);
+        }
     }
 }
+static_assert(SMP_THREADS * 8 == 1 << 13, "the owner of a vocabulary index is decoded with shifts");
 
 // (pos, step) += 1 outside a decode step (the decode step's embed kernel advances them itself).
 __global__ void advance_state_kernel(int* state) {
@@ -502,11 +524,12 @@ __global__ void advance_state_kernel(int* state) {
 static int sample_impl(const void* logits, const float* noise, long long noise_step_stride, int* cur_tok, int* seq,
                        const int* state, int B, int V, int seq_stride, int use_cfg, float cfg_scale,
                        int cfg_interval, float temperature, int top_k, float top_p, int greedy, int dtype,
-                       int* row_step, int* row_pos, int max_steps, const lgen_slot_sampling* params, void* stream) {
+                       int* row_step, int* row_pos, int max_steps, const lgen_slot_sampling* params, float* logprob,
+                       void* stream) {
     if (V > SMP_MAXV || V < 8 || (V & 7) || B < 1) return LGEN_ERR_BAD_ARG;
     if (!params && !greedy && !noise) return LGEN_ERR_BAD_ARG;  // with records `greedy` lives on the device: the caller's contract
     SampleArgs a{logits, noise, noise_step_stride, cur_tok, seq, state, B, V, seq_stride, use_cfg, cfg_scale,
-                 temperature, top_p, cfg_interval, top_k, greedy, row_step, row_pos, max_steps, params};
+                 temperature, top_p, cfg_interval, top_k, greedy, row_step, row_pos, max_steps, params, logprob};
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = (size_t)SMP_MAXV * sizeof(float);
     static unsigned long long attr_set_mask = 0;   // per device
@@ -535,7 +558,19 @@ extern "C" int lgen_sample(const void* logits, const float* noise, long long noi
                            int cfg_interval, float temperature, int top_k, float top_p, int greedy, int dtype,
                            void* stream) {
     return sample_impl(logits, noise, noise_step_stride, cur_tok, seq, state, B, V, seq_stride, use_cfg, cfg_scale, cfg_interval,
-                       temperature, top_k, top_p, greedy, dtype, nullptr, nullptr, 0, nullptr, stream);
+                       temperature, top_k, top_p, greedy, dtype, nullptr, nullptr, 0, nullptr, nullptr, stream);
+}
+
+// lgen_sample + the sampled token's log-probability (serve/sampler.py:88-93 log_softmax of the final sampling distribution,
+// :119-123 _get_logprobs): logprob_out[b * seq_stride + step], fp32, indexed like seq.  Tokens and every other output are those of
+// lgen_sample, bit for bit.
+extern "C" int lgen_sample_logprob(const void* logits, const float* noise, long long noise_step_stride, int* cur_tok, int* seq,
+                                   const int* state, int B, int V, int seq_stride, int use_cfg, float cfg_scale,
+                                   int cfg_interval, float temperature, int top_k, float top_p, int greedy, int dtype,
+                                   float* logprob_out, void* stream) {
+    if (!logprob_out) return LGEN_ERR_BAD_ARG;
+    return sample_impl(logits, noise, noise_step_stride, cur_tok, seq, state, B, V, seq_stride, use_cfg, cfg_scale, cfg_interval,
+                       temperature, top_k, top_p, greedy, dtype, nullptr, nullptr, 0, nullptr, logprob_out, stream);
 }
 
 // Continuous batching form (autoregressive/serve/sampler.py:54-58,106-108: paired cond / uncond sequences, every request at its
@@ -546,7 +581,7 @@ extern "C" int lgen_sample_rows(const void* logits, const float* noise, int* cur
                                 float temperature, int top_k, float top_p, int greedy, int dtype, void* stream) {
     if (!row_step || !row_pos || max_steps < 1) return LGEN_ERR_BAD_ARG;
     return sample_impl(logits, noise, 0, cur_tok, seq, nullptr, B, V, seq_stride, use_cfg, cfg_scale, cfg_interval, temperature,
-                       top_k, top_p, greedy, dtype, row_step, row_pos, max_steps, nullptr, stream);
+                       top_k, top_p, greedy, dtype, row_step, row_pos, max_steps, nullptr, nullptr, stream);
 }
 
 // Per-request form (serve/sampler.py:54-58,65-83,106-108: one SamplingParams per sequence): lgen_sample_rows with the six sampling
@@ -559,7 +594,17 @@ extern "C" int lgen_sample_rows_params(const void* logits, const float* noise, i
                                        int dtype, void* stream) {
     if (!params || !row_step || !row_pos || max_steps < 1) return LGEN_ERR_BAD_ARG;
     return sample_impl(logits, noise, 0, cur_tok, seq, nullptr, B, V, seq_stride, use_cfg, 1.0f, -1, 1.0f, 0, 1.0f, 0, dtype, row_step,
-                       row_pos, max_steps, params, stream);
+                       row_pos, max_steps, params, nullptr, stream);
+}
+
+// lgen_sample_rows_params + the sampled token's log-probability under the SLOT's final sampling distribution: logprob_out
+// [B][seq_stride] fp32, slot (b, row_step[b]) as for seq; a skipped slot writes nothing.
+extern "C" int lgen_sample_rows_params_logprob(const void* logits, const float* noise, int* cur_tok, int* seq, int* row_step,
+                                               int* row_pos, int max_steps, int B, int V, int seq_stride, int use_cfg,
+                                               const lgen_slot_sampling* params, int dtype, float* logprob_out, void* stream) {
+    if (!params || !row_step || !row_pos || max_steps < 1 || !logprob_out) return LGEN_ERR_BAD_ARG;
+    return sample_impl(logits, noise, 0, cur_tok, seq, nullptr, B, V, seq_stride, use_cfg, 1.0f, -1, 1.0f, 0, 1.0f, 0, dtype, row_step,
+                       row_pos, max_steps, params, logprob_out, stream);
 }
 
 extern "C" int lgen_advance_state(int* state, void* stream) {

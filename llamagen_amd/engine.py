@@ -173,6 +173,7 @@ class DecodeEngine:
         self.noise = None            # [N][B][V] fp32 Exp(1) draws of one generate() (allocated on demand)
         self.cur_tok = z(mts * 16, dtype=torch.int32)
         self.seq = z(max_batch, S8 + 8, dtype=torch.int32)
+        self.logp = z(max_batch, S8 + 8, dtype=torch.float32)  # log-probability of seq's tokens (written only when asked for)
         self.state = z(2, dtype=torch.int32)                 # [pos, step]
         # The decode / prefill attention consults `causal_mask` (the tensor Transformer.setup_caches exposes as
         # model.causal_mask, writable like the reference's, generate.py:154-163) whenever the model is t2i: a caller
@@ -430,21 +431,29 @@ class DecodeEngine:
             L.check(self.lib.lgen_ssq_pack(L.ptr(self.hp), L.ptr(self.ssq), self.MTs, self.d, self.dt, L.stream()), "ssq_pack")
         self.ssq_parts = self.d // 16
 
-    def _sample(self, B, sp):
-        """CFG mix + top-k + softmax + argmax(p/q) for the token at step = state[1]; q = noise[step]."""
+    def _sample(self, B, sp, logp=None):
+        """CFG mix + top-k + softmax + argmax(p/q) for the token at step = state[1]; q = noise[step].  `logp` (fp32, shaped like
+        `seq`): also the sampled token's log-probability, at the slot `seq` takes the token (serve/sampler.py:88-93,119-123)."""
         greedy = 0 if sp["sample_logits"] else 1
         stride = B * self.V if not greedy else 0
-        L.check(self.lib.lgen_sample(L.ptr(self.logits), 0 if greedy else L.ptr(self.noise), stride, L.ptr(self.cur_tok),
-                                     L.ptr(self.seq), L.ptr(self.state), B, self.V, self.seq.shape[1],
-                                     1 if sp["use_cfg"] else 0, float(sp["cfg_scale"]), int(sp["cfg_interval"]),
-                                     float(sp["temperature"]), int(sp["top_k"]), float(sp["top_p"]), greedy, self.dt,
-                                     L.stream()), "lgen_sample")
+        args = (L.ptr(self.logits), 0 if greedy else L.ptr(self.noise), stride, L.ptr(self.cur_tok),
+                L.ptr(self.seq), L.ptr(self.state), B, self.V, self.seq.shape[1],
+                1 if sp["use_cfg"] else 0, float(sp["cfg_scale"]), int(sp["cfg_interval"]),
+                float(sp["temperature"]), int(sp["top_k"]), float(sp["top_p"]), greedy, self.dt)
+        if logp is None:
+            L.check(self.lib.lgen_sample(*args, L.stream()), "lgen_sample")
+        else:
+            assert logp.shape == self.seq.shape and logp.dtype == torch.float32
+            L.check(self.lib.lgen_sample_logprob(*args, L.ptr(logp), L.stream()), "lgen_sample_logprob")
+
+    def _logp_of(self, sp):
+        return self.logp if sp.get("return_logprobs") else None
 
     def decode_step(self, B, sp):
         """One KV-cached decode step: advance (pos, step); embed(cur_tok) -> L blocks -> logits -> sample."""
         self._embed(self.tok_emb, self.cur_tok, advance=True)
         self._layers_and_logits()
-        self._sample(B, sp)
+        self._sample(B, sp, self._logp_of(sp))
 
     # ---- t2i prefix (CaptionEmbedder, gpt.py:110-131) ------------------------------------------
     def caption_embed(self, cond: torch.Tensor) -> torch.Tensor:
@@ -526,11 +535,49 @@ class DecodeEngine:
             ws = self._run_sequence(emb)
         finally:
             self._force_causal = False
-        lib, st, dt, mts, R = self.lib, L.stream(), self.dt, ws["mts"], ws["R"]
+        return self._sequence_logit_rows(ws)[:ws["R"]].view(S, B2, self.V).transpose(0, 1).float().contiguous()
+
+    def _sequence_logit_rows(self, ws):
+        """norm + output (gpt.py:367-368) on the final residual stream of _run_sequence: storage-dtype logits [mts * 16, V],
+        row r = t * B2 + b (rows >= R are padding)."""
+        lib, st, dt, mts, R, d = self.lib, L.stream(), self.dt, ws["mts"], ws["R"], self.d
         L.check(lib.lgen_rmsnorm(L.ptr(ws["hp"]), L.ptr(self.norm_w), L.ptr(ws["xn"]), mts, d, self.eps, dt, st), "rmsnorm")
         lg = torch.empty(mts * 16, self.V, dtype=self.dtype, device=self.dev)
         self.gemm(self.out_w, ws["xn"], lg, R, mts, self.V, d, L.EPI_ROWS, (min(mts, 4), 1, max(1, min(8, (d // self.kc) // 2))))
-        return lg[:R].view(S, B2, self.V).transpose(0, 1).float().contiguous()
+        return lg
+
+    def score_sequence(self, model, cond_combined, ids, B, emb_masks, cfg_scale, temperature):
+        """log p(ids[b, j] | cond, ids[b, :j]) under the CFG-mixed, temperature-scaled model, fp32 [B, N]: ONE teacher-forced pass
+        over cond ++ tok_emb[ids[:, :-1]] (the positions generate() visits one by one, with the same mask), lm_head in the storage
+        dtype, then lgen_logprob_rows on its rows -- no fp32 [B, S, V] logits, no softmax of width V in memory (what
+        gpt.py:373-380 does for the cross-entropy).  cond_combined: the B2 = B or 2B conditioning rows of generate() (conditional
+        rows, then their unconditional twins); emb_masks: [B2, T] or None."""
+        N = ids.shape[1]
+        if model.model_type == "c2i":
+            cond = self.cls_emb[cond_combined.reshape(-1).long()].unsqueeze(1)
+        else:
+            cond = self.caption_embed(cond_combined)
+        cond = cond[:, : self.T]
+        T, B2 = cond.shape[1], cond.shape[0]
+        if T + N > self.S8 or T + N - 1 > self.freqs_cis.shape[0]:
+            raise IndexError(f"{T} + {N} tokens exceed the caches ({self.S8} slots) / RoPE table ({self.freqs_cis.shape[0]} rows)")
+        ids = ids.to(device=self.dev, dtype=torch.int32)
+        fed = ids[:, :-1].long().repeat(B2 // B, 1)                                 # the twins are fed the same tokens
+        emb = torch.cat([cond, self.tok_emb[fed]], dim=1)                           # [B2, T + N - 1, d]
+        if emb_masks is not None:  # generate.py:154-163, as generate_iter folds them
+            cm = self.causal_mask
+            cm[:, :, :T] = cm[:, :, :T] & emb_masks.to(self.dev).ne(0).unsqueeze(1)
+            cm |= torch.eye(self.S8, dtype=torch.bool, device=self.dev)
+            self.use_mask = True
+        ws = self._run_sequence(emb)
+        lg = self._sequence_logit_rows(ws)
+        S = T + N - 1
+        tg = torch.full((lg.shape[0],), -1, dtype=torch.int32, device=self.dev)     # rows r = t * B2 + b; only (t >= T - 1, b < B) score
+        tg[: S * B2].view(S, B2)[T - 1:, :B] = ids.t()
+        out = torch.zeros(lg.shape[0], dtype=torch.float32, device=self.dev)
+        L.check(self.lib.lgen_logprob_rows(L.ptr(lg), L.ptr(tg), L.ptr(out), S * B2, self.V, B if B2 > B else 0, float(cfg_scale),
+                                           float(temperature), self.dt, L.stream()), "lgen_logprob_rows")
+        return out[: S * B2].view(S, B2)[T - 1:, :B].t().contiguous()
 
     def _final_logits(self):
         """norm + output on the decode workspace (gpt.py:367-368) after the t2i prefill: on the SKINNY kernels at every chain width
@@ -566,7 +613,8 @@ class DecodeEngine:
 
     # ---- the generate() loop ---------------------------------------------------------------
     def generate(self, model, cond_combined, B, max_new_tokens, emb_masks, sp):
-        """prefill + (N-1) decode steps; returns int32 [B, N].  sp: sampling parameter dict."""
+        """prefill + (N-1) decode steps; returns int32 [B, N] (with sp["return_logprobs"]: and fp32 [B, N] log-probabilities).
+        sp: sampling parameter dict."""
         it = self.generate_iter(model, cond_combined, B, max_new_tokens, emb_masks, sp)
         while True:
             try:
@@ -609,14 +657,15 @@ class DecodeEngine:
                 self._prefill_prefix(emb)
                 self.state[0] = T - 1
                 self._final_logits()
-        self._sample(B, sp)
+        logp = self._logp_of(sp)
+        self._sample(B, sp, logp)
         yield 0
         # ---- decode (generate.py:105-123): every step first advances (pos, step)
         key = (B, N, self._mask() is not None, self.fuse_norm, self.use_tile, tuple(sorted(self.tile_shape_override.items())),
                tuple(sorted(self.tile_override.items())),
                tuple(sorted(self.pass_override.items())), sp["use_cfg"], sp["cfg_scale"],
                sp["cfg_interval"], sp["temperature"], sp["top_k"], sp["top_p"], sp["sample_logits"],
-               self.noise.data_ptr() if sampling else 0)
+               self.noise.data_ptr() if sampling else 0, logp is not None)
         use_graph = os.environ.get("LGEN_NO_GRAPH") is None and N > 3
         i = 1
         if use_graph:
@@ -640,6 +689,8 @@ class DecodeEngine:
                 self.decode_step(B, sp)
                 i += 1
                 yield i - 1
+        if logp is not None:
+            return self.seq[:B, :N].clone(), logp[:B, :N].clone()
         return self.seq[:B, :N].clone()
 
     # ---- Transformer.forward inference branches (gpt.py:347-368) ---------------------------------

@@ -14,7 +14,9 @@ import torch
 
 @torch.no_grad()
 def generate(model, cond, max_new_tokens, emb_masks=None, cfg_scale=1.0, cfg_interval=-1, **sampling_kwargs):
-    """Drop-in generate(): runs the step generator below to completion on the current stream."""
+    """Drop-in generate(): runs the step generator below to completion on the current stream.
+    return_logprobs=True (keyword): returns (ids int32 [B, N], logprobs fp32 [B, N]) -- every token's log-probability under the
+    distribution it was drawn from (after CFG mix, temperature, top-k and top-p; serve/sampler.py:88-93,119-123)."""
     it = generate_iter(model, cond, max_new_tokens, emb_masks, cfg_scale, cfg_interval, **sampling_kwargs)
     while True:
         try:
@@ -42,12 +44,13 @@ def _null_condition(model, cond):
 
 def generate_iter(model, cond, max_new_tokens, emb_masks=None, cfg_scale=1.0, cfg_interval=-1, **sampling_kwargs):
     """Same arguments as generate(); a generator that yields after every enqueued decode step and returns
-    the int32 [B, N] ids (StopIteration.value).  Call it (and every next()) with the lane's stream current
-    and under torch.no_grad()."""
+    the int32 [B, N] ids (StopIteration.value; with return_logprobs=True the pair (ids, fp32 [B, N] log-probabilities)).
+    Call it (and every next()) with the lane's stream current and under torch.no_grad()."""
     temperature = sampling_kwargs.pop("temperature", 1.0)
     top_k = sampling_kwargs.pop("top_k", 0)
     top_p = sampling_kwargs.pop("top_p", 1.0)
     sample_logits = sampling_kwargs.pop("sample_logits", True)
+    return_logprobs = bool(sampling_kwargs.pop("return_logprobs", False))
     noise_seq = sampling_kwargs.pop("_noise_seq", None)  # test hook: inject the Exp(1) draws [N, B, V]
     # pipeline hook (llamagen_amd/pipeline.py, batches_per_chain > 1): `cond` is the FIRST batch of a chain and these callables
     # yield the conditioning of the batches that share its decode chain.  They are evaluated in the order consecutive reference
@@ -100,8 +103,35 @@ def generate_iter(model, cond, max_new_tokens, emb_masks=None, cfg_scale=1.0, cf
     sp = dict(use_cfg=use_cfg, cfg_scale=float(cfg_scale), cfg_interval=int(cfg_interval),
               temperature=float(temperature), top_k=int(top_k), top_p=float(top_p),
               sample_logits=bool(sample_logits))
+    if return_logprobs:
+        sp["return_logprobs"] = True
     if noise_seq is not None:
         sp["_noise_seq"] = noise_seq
     if prefilled:
         sp["_noise_prefilled"] = True
     return (yield from model._engine.generate_iter(model, rows, B, max_new_tokens, masks, sp))
+
+
+@torch.no_grad()
+def score(model, cond, ids, emb_masks=None, cfg_scale=1.0, temperature=1.0):
+    """log p(ids[:, t] | cond, ids[:, :t]) under the CFG-mixed, temperature-scaled model: fp32 [B, N].  `cond`, `emb_masks` and
+    `cfg_scale` mean what they mean for generate() (class ids [B], or caption embeddings [B, T, C] with their [B, T] masks); ids is
+    [B, N] token ids.  One teacher-forced pass and a fused log-softmax-gather kernel: the sum over t is the sequence
+    log-likelihood that ranks candidates, its negative mean the validation NLL (gpt.py:373-380) -- without fp32 [B, S, V] logits."""
+    kind = model.model_type
+    if kind not in ("c2i", "t2i"):
+        raise Exception("please check model type")
+    if ids.dim() != 2 or ids.shape[0] != cond.shape[0] or ids.shape[1] < 1:
+        raise ValueError("ids must be [B, N] with one row per conditioning row")
+    use_cfg = cfg_scale > 1.0
+    prefix = 1 if kind == "c2i" else cond.shape[1]
+    B = cond.shape[0]
+    rows = torch.cat([cond, _null_condition(model, cond)]) if use_cfg else cond
+    model.setup_caches(max_batch_size=rows.shape[0], max_seq_length=prefix + ids.shape[1], dtype=model.tok_embeddings.weight.dtype)
+    masks = None
+    if emb_masks is not None:
+        assert emb_masks.shape[0] == B and emb_masks.shape[-1] == prefix
+        masks = emb_masks.repeat(2, *([1] * (emb_masks.dim() - 1))) if use_cfg else emb_masks
+    if kind == "c2i":
+        rows = rows.to(torch.int32)
+    return model._engine.score_sequence(model, rows, ids, B, masks, cfg_scale, temperature)

@@ -32,6 +32,12 @@ slot-indexed device tensor that the sampler kernel reads (lgen_sample_rows_param
 is fixed by the constructor (it fixes the row layout and the captured graphs): an unguided request in a guided batcher samples its
 conditional logits unchanged and still pays for its unconditional row.
 
+Log-probabilities and best-of-N (serve/sampler.py:88-93,119-123 the sampled token's log-probability under the final sampling
+distribution, :357-365 `cumulative_logprob`, serve/llm.py `best_of`): every step also writes the token's log-probability into a
+slot-indexed buffer (lgen_sample_rows_params_logprob: the same tokens, one more float per slot); `run(return_outputs=True)` returns
+RequestOutput records.  `SamplingParams(best_of=k)` runs k candidates of one request in k slots (seed + j each) and answers with
+the likeliest; the choice is an argmax on the device, nothing waits for it.
+
 Every request produces exactly the tokens a batch-of-one `generate()` would with the same noise and sampling values: rows are
 independent through every kernel (tests/test_gpu_serve.py and tests/test_gpu_serve_params.py hold that to the oracle, token for
 token, in fp32).
@@ -70,6 +76,27 @@ def pick_bucket(sizes: Sequence[int], live: int) -> int:
     return sizes[-1]
 
 
+def pick_best(cumulative: Sequence[float]) -> int:
+    """The `best_of` winner: the candidate with the largest cumulative log-probability, the lowest index among equals (what
+    torch.argmax gives the device-side selection: the first maximum)."""
+    best = 0
+    for j in range(1, len(cumulative)):
+        if cumulative[j] > cumulative[best]:
+            best = j
+    return best
+
+
+def check_best_of(sampling: "SamplingParams", slots: int, has_noise: bool = False) -> int:
+    """The number of slots a request's candidates take, or ValueError: every candidate needs a slot of its own, and k candidates
+    cannot share one explicit noise block."""
+    k = int(sampling.best_of)
+    if k > int(slots):
+        raise ValueError(f"best_of {k} exceeds the batcher's {slots} slots")
+    if k > 1 and has_noise:
+        raise ValueError("best_of > 1 draws one noise block per candidate: give a seed, not `noise`")
+    return k
+
+
 def plan_moves(active: Sequence[bool], new_slots: int):
     """(old slot, new slot) for every running request when the slot count becomes `new_slots`: a request keeps its index when
     that still exists, otherwise it takes the lowest free one."""
@@ -91,6 +118,8 @@ class SamplingParams:
     top_p: float = 1.0
     sample_logits: bool = True
     seed: Optional[int] = None
+    logprobs: bool = False      # informational (the batcher records every token's log-probability anyway): ask for RequestOutputs
+    best_of: int = 1            # candidates drawn for this request; the likeliest (largest cumulative log-probability) is returned
 
     def __post_init__(self):
         for name in ("cfg_scale", "temperature", "top_p"):
@@ -102,6 +131,19 @@ class SamplingParams:
             raise ValueError(f"top_k must be >= 0 (0 = off), got {self.top_k}")
         if int(self.top_k) != self.top_k or int(self.cfg_interval) != self.cfg_interval:
             raise ValueError("top_k and cfg_interval are integers")
+        if isinstance(self.best_of, bool) or int(self.best_of) != self.best_of or int(self.best_of) < 1:
+            raise ValueError(f"best_of must be an integer >= 1, got {self.best_of}")
+        if int(self.best_of) > 1 and not self.sample_logits:
+            raise ValueError("best_of > 1 needs sample_logits=True (greedy candidates are all the same)")
+
+
+@dataclasses.dataclass
+class RequestOutput:
+    """What one request produced (the fields of the vLLM fork's CompletionOutput this project fills): device tensors, enqueued on
+    the current stream."""
+    token_ids: torch.Tensor            # int32 [N]
+    logprobs: torch.Tensor             # fp32 [N]: log-probability of each token under the distribution it was drawn from
+    cumulative_logprob: torch.Tensor   # 0-d float64: logprobs.double().sum() (serve/sampler.py:357-365)
 
 
 def pack_sampling(sp: SamplingParams) -> np.ndarray:
@@ -132,6 +174,8 @@ class _Bucket:
 
 
 class ContinuousBatcher:
+    logp = None   # a subclass that builds its own state without log-probabilities (the CPU stand-ins of tests/) has no buffer
+
     def __init__(self, model, slots: int, max_new_tokens: int, cfg_scale: float = 1.0, cfg_interval: int = -1,
                  temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, sample_logits: bool = True,
                  slot_buckets: Optional[Sequence[int]] = None, shrink_after: int = 8):
@@ -160,6 +204,9 @@ class ContinuousBatcher:
         self.row_step = torch.full((slots,), max_new_tokens, dtype=torch.int32, device=dev)  # >= N: empty slot
         self.noise = torch.empty(slots, max_new_tokens, self.V, dtype=torch.float32, device=dev) if sample_logits else None
         self.seq = torch.zeros(slots, max_new_tokens, dtype=torch.int32, device=dev)
+        self.logp = torch.zeros(slots, max_new_tokens, dtype=torch.float32, device=dev)   # log-probability of seq's tokens
+        self._cand: Dict[int, tuple] = {}      # candidate id -> (request id, j) of a best_of request
+        self._group: Dict[int, list] = {}      # request id -> its candidates' RequestOutputs (None until finished)
         # the constructor's sampling values: what a request that brings no SamplingParams gets
         self.defaults = SamplingParams(cfg_scale=float(cfg_scale), cfg_interval=int(cfg_interval), temperature=float(temperature),
                                        top_k=int(top_k), top_p=float(top_p), sample_logits=bool(sample_logits))
@@ -218,6 +265,8 @@ class ContinuousBatcher:
                 if self.noise is not None:
                     self.noise[t].copy_(self.noise[s])
                 self.seq[t].copy_(self.seq[s])
+                if self.logp is not None:
+                    self.logp[t].copy_(self.logp[s])
                 if getattr(self, "params", None) is not None:
                     self.params[t].copy_(self.params[s])
                 self.row_step[t:t + 1].copy_(self.row_step[s:s + 1])
@@ -244,6 +293,7 @@ class ContinuousBatcher:
                 raise ValueError("cfg_scale > 1 needs a batcher built with cfg_scale > 1 (the step batch has no unconditional rows)")
             if sampling.sample_logits and self.noise is None:
                 raise ValueError("sample_logits=True needs a batcher built with sample_logits=True (a greedy batcher has no noise buffer)")
+            check_best_of(sampling, self.slots, noise is not None)
         if self.t2i:
             cap = class_label
             if not torch.is_tensor(cap) or cap.dim() != 2 or cap.shape[0] != self.T:
@@ -262,6 +312,19 @@ class ContinuousBatcher:
                 raise ValueError(f"noise must be [{self.N}, {self.V}] fp32 Exp(1) draws, got {tuple(noise.shape)}")
         rid = self._next_id
         self._next_id += 1
+        if sampling is not None and sampling.best_of > 1:
+            # k candidates of ONE request: k queue entries with ids of their own (never handed out), the same conditioning and
+            # seed + j; _output() answers under `rid` with the likeliest once the last one is through
+            k = int(sampling.best_of)
+            self.__dict__.setdefault("_group", {})[rid] = [None] * k
+            for j in range(k):
+                cid = self._next_id
+                self._next_id += 1
+                self.__dict__.setdefault("_cand", {})[cid] = (rid, j)
+                self.__dict__.setdefault("_req_sampling", {})[cid] = dataclasses.replace(sampling, best_of=1,
+                                                              seed=None if sampling.seed is None else int(sampling.seed) + j)
+                self._queue.append((cid, label, None))
+            return rid
         if sampling is not None:   # a side table, not a fourth queue field: the queue entries stay (rid, label, noise)
             self.__dict__.setdefault("_req_sampling", {})[rid] = sampling
         self._queue.append((rid, label, noise))
@@ -329,7 +392,7 @@ class ContinuousBatcher:
         first = dict(use_cfg=self.use_cfg and sp.cfg_scale > 1.0, cfg_scale=sp.cfg_scale, cfg_interval=sp.cfg_interval,
                      temperature=sp.temperature, top_k=sp.top_k, top_p=sp.top_p, sample_logits=sp.sample_logits)
         pe.noise = self.noise[b].view(self.N, 1, self.V) if self.noise is not None else None
-        pe._sample(1, first)   # writes cur_tok[0]; both step-batch rows take it below
+        pe._sample(1, first, pe.logp)   # writes cur_tok[0]; both step-batch rows take it below
         for src, dst in ((0, b),) + (((1, self.B + b),) if self.use_cfg else ()):
             e.k_cache[:, dst, :, :T].copy_(pe.k_cache[:, src, :, :T])
             e.v_cache[:, dst, :, :T].copy_(pe.v_cache[:, src, :, :T])
@@ -337,6 +400,7 @@ class ContinuousBatcher:
             e.cur_tok[dst:dst + 1].copy_(pe.cur_tok[0:1])
             self.row_pos[dst] = T
         self.seq[b, 0:1].copy_(pe.seq[0, 0:1])
+        self.logp[b, 0:1].copy_(pe.logp[0, 0:1])
         self.row_step[b] = 1
 
     # ---- one step of the whole slot batch -------------------------------------------------------------------------------
@@ -349,13 +413,16 @@ class ContinuousBatcher:
         e.ssq_parts = e.d // 16
         e._layers_and_logits()
         # noise is null only in a batcher built greedy, and submit() lets no sampled request into one (the kernel's contract)
-        L.check(lib.lgen_sample_rows_params(L.ptr(e.logits), L.ptr(self.noise), L.ptr(e.cur_tok), L.ptr(self.seq), L.ptr(self.row_step),
-                                            L.ptr(self.row_pos), self.N, self.B, e.V, self.N, 1 if self.use_cfg else 0,
-                                            L.ptr(self.params), e.dt, L.stream()), "sample_rows_params")
+        L.check(lib.lgen_sample_rows_params_logprob(L.ptr(e.logits), L.ptr(self.noise), L.ptr(e.cur_tok), L.ptr(self.seq),
+                                                    L.ptr(self.row_step), L.ptr(self.row_pos), self.N, self.B, e.V, self.N,
+                                                    1 if self.use_cfg else 0, L.ptr(self.params), e.dt, L.ptr(self.logp),
+                                                    L.stream()), "sample_rows_params_logprob")
 
-    def run(self, use_graph: bool = True) -> Dict[int, torch.Tensor]:
-        """Drain the queue; returns {request id: int32 [N] token ids} (device tensors, enqueued on the current stream)."""
-        done: Dict[int, torch.Tensor] = {}
+    def run(self, use_graph: bool = True, return_outputs: bool = False):
+        """Drain the queue; returns {request id: int32 [N] token ids} (device tensors, enqueued on the current stream), with
+        return_outputs=True {request id: RequestOutput} (tokens, per-token log-probabilities and their sum)."""
+        done: Dict[int, object] = {}
+        full = bool(return_outputs)
         with torch.no_grad():
             while self._queue or any(r is not None for r in self._slot_req):
                 if len(self.bucket_sizes) > 1:
@@ -367,7 +434,7 @@ class ContinuousBatcher:
                     if self.cur.graph is None:
                         self._step()  # warm every kernel once, eagerly
                         self.steps_run += 1
-                        self._account(done)
+                        self._account(done, full)
                         g = torch.cuda.CUDAGraph()
                         torch.cuda.synchronize()
                         with torch.cuda.graph(g):
@@ -378,16 +445,40 @@ class ContinuousBatcher:
                 else:
                     self._step()
                 self.steps_run += 1
-                self._account(done)
+                self._account(done, full)
         return done
 
-    def _account(self, done):
+    def _output(self, b: int, full: bool):
+        """(request id, result) of slot b's finished request, called right after the step that wrote its last token was enqueued:
+        the tokens, or with `full` a RequestOutput; (None, None) for a best_of candidate whose request still has others running."""
+        cid = self._slot_req[b]
+        cand = self.__dict__.get("_cand", {})
+        if cid not in cand and not full:
+            return cid, self.seq[b].clone()
+        lp = self.logp[b].clone()
+        out = RequestOutput(self.seq[b].clone(), lp, lp.double().sum())
+        if cid not in cand:
+            return cid, out
+        rid, j = cand.pop(cid)
+        group = self._group[rid]
+        group[j] = out
+        if any(o is None for o in group):
+            return None, None
+        del self._group[rid]
+        # pick_best() on the device: argmax returns the first maximum, index_select takes its row -- no host sync
+        win = torch.stack([o.cumulative_logprob for o in group]).argmax().view(1)
+        take = lambda name: torch.stack([getattr(o, name) for o in group]).index_select(0, win)[0]
+        return rid, RequestOutput(take("token_ids"), take("logprobs"), take("cumulative_logprob")) if full else take("token_ids")
+
+    def _account(self, done, full: bool = False):
         for b in range(self.B):
             if self._slot_req[b] is None:
                 continue
             self._slot_left[b] -= 1
             if self._slot_left[b] == 0:  # the step just enqueued wrote this request's last token
-                done[self._slot_req[b]] = self.seq[b].clone()
+                rid, out = self._output(b, full)
+                if rid is not None:
+                    done[rid] = out
                 self._slot_req[b] = None
                 self.row_pos[b] = 1          # park the rows again (after that step, stream-ordered): an idle row at its final
                 if self.use_cfg:             # position would keep costing the attention a full sequence
