@@ -493,22 +493,25 @@ class DecodeEngine:
             self._pf_ws = ws
         rows = emb.transpose(0, 1).reshape(R, d).to(self.dtype)  # r = t * B2 + b
         ws["hp"].copy_(pack_act(rows.contiguous(), mts).view_as(ws["hp"]))
-        mt = min(mts, 4)
-        tile = lambda N, K: (mt, 1, max(1, min(8, (K // self.kc) // 2)))
+        tile = lambda K, nt=1: self._sequence_tiles(mts, K, nt)
         pm = self._mask()
         for i, w in enumerate(self.layers):
             L.check(lib.lgen_rmsnorm(L.ptr(ws["hp"]), L.ptr(w["an"]), L.ptr(ws["xn"]), mts, d, self.eps, dt, st), "rmsnorm")
-            self.gemm(w["wqkv"], ws["xn"], ws["qkv"], R, mts, 3 * d, d, L.EPI_PACKED, tile(3 * d, d))
+            self.gemm(w["wqkv"], ws["xn"], ws["qkv"], R, mts, 3 * d, d, L.EPI_PACKED, tile(d))
             L.check(lib.lgen_rope_append_prefill(L.ptr(ws["qkv"]), L.ptr(ws["q"]), L.ptr(self.k_cache[i]), L.ptr(self.v_cache[i]),
                                                  L.ptr(self.freqs_cis), R, B2, mts, d, H, hd, hdp, S8, self.kvs, 0, dt, st),
                     "rope_append_prefill")
             L.check(lib.lgen_attn_prefill(L.ptr(ws["q"]), L.ptr(self.k_cache[i]), L.ptr(self.v_cache[i]), L.ptr(ws["ap"]), L.ptr(pm),
                                           T, B2, mts, H, hd, hdp, S8, self.kvs, dt, st), "attn_prefill")
-            self.gemm(w["wo"], ws["ap"], ws["hp"], R, mts, d, d, L.EPI_RES, tile(d, d))
+            self.gemm(w["wo"], ws["ap"], ws["hp"], R, mts, d, d, L.EPI_RES, tile(d))
             L.check(lib.lgen_rmsnorm(L.ptr(ws["hp"]), L.ptr(w["fn"]), L.ptr(ws["xn"]), mts, d, self.eps, dt, st), "rmsnorm")
-            self.gemm(w["w13"], ws["xn"], ws["gp"], R, mts, 2 * F, d, L.EPI_SWIGLU, (mt, 2, max(1, min(8, (d // self.kc) // 2))))
-            self.gemm(w["w2"], ws["gp"], ws["hp"], R, mts, d, F, L.EPI_RES, tile(d, F))
+            self.gemm(w["w13"], ws["xn"], ws["gp"], R, mts, 2 * F, d, L.EPI_SWIGLU, tile(d, nt=2))
+            self.gemm(w["w2"], ws["gp"], ws["hp"], R, mts, d, F, L.EPI_RES, tile(F))
         return ws
+
+    def _sequence_tiles(self, mts, K, nt=1):
+        """(mt, nt, kw) of the skinny kernel for a GEMM of the prefill / whole-sequence pass (many rows, reduction length K)."""
+        return min(mts, 4), nt, max(1, min(8, (K // self.kc) // 2))
 
     def _prefill_prefix(self, emb: torch.Tensor):
         """emb [B2, T, d] (CaptionEmbedder output) -> KV slots 0..T-1 of every layer filled, residual stream of
@@ -518,17 +521,34 @@ class DecodeEngine:
         last = unpack_act(ws["hp"], ws["R"])[(T - 1) * B2:]
         self._set_residual(last)
 
+    def _cond_rows(self, model, cond):
+        """cls_embedding(cond)[:, :T] (gpt.py:341-346): rows of the class table (LabelEmbedder in eval mode, gpt.py:78-83) or the
+        CaptionEmbedder MLP (gpt.py:110-131) -> [B2, T, d]."""
+        if model.model_type == "c2i":
+            return self.cls_emb[cond.reshape(-1).long()].unsqueeze(1)[:, : self.T]
+        return self.caption_embed(cond)[:, : self.T]
+
+    def _check_capacity(self, T, N):
+        """T conditioning positions + N image tokens must fit the KV slots and (all but the last token) the RoPE table."""
+        if T + N > self.S8 or T + N - 1 > self.freqs_cis.shape[0]:
+            raise IndexError(f"{T} + {N} tokens exceed the caches ({self.S8} slots) / RoPE table ({self.freqs_cis.shape[0]} rows)")
+
+    def fold_emb_masks(self, emb_masks, T):
+        """generate.py:154-163: AND the validity of the T (left-padded) caption tokens, [B2, T] or [1, T] for every row alike, into
+        the prefix columns of causal_mask, force the diagonal, and have the attention consult the mask.  None: nothing to fold."""
+        if emb_masks is None:
+            return
+        cm = self.causal_mask
+        cm[:, :, :T] = cm[:, :, :T] & emb_masks.to(self.dev).ne(0).unsqueeze(1)
+        cm |= torch.eye(self.S8, dtype=torch.bool, device=self.dev)
+        self.use_mask = True
+
     def forward_sequence(self, model, idx, cond_idx):
         """Teacher-forced forward over a whole sequence (gpt.py:341-346, 357-368 with `is_causal` attention):
         rows = cls_embedding(cond_idx)[:, :T] ++ tok_embeddings(idx) -> fp32 logits [B, T + n, V] (values carry
         the storage dtype's rounding, gpt.py:368).  The reference runs this shape without KV caches; here the
         K/V of every position land in the engine's slabs (slots 0..T+n-1) as a side effect."""
-        if model.model_type == "c2i":
-            cond = self.cls_emb[cond_idx.reshape(-1).long()].unsqueeze(1)       # LabelEmbedder, eval (gpt.py:78-83)
-        else:
-            cond = self.caption_embed(cond_idx)                                    # CaptionEmbedder (gpt.py:110-131)
-        cond = cond[:, : self.T]
-        emb = torch.cat([cond, self.tok_emb[idx.long()]], dim=1)                  # [B, T + n, d]
+        emb = torch.cat([self._cond_rows(model, cond_idx), self.tok_emb[idx.long()]], dim=1)   # [B, T + n, d]
         B2, S, d = emb.shape
         self._force_causal = True  # this shape is `is_causal` in the reference (gpt.py:234), no emb_masks
         try:
@@ -543,7 +563,7 @@ class DecodeEngine:
         lib, st, dt, mts, R, d = self.lib, L.stream(), self.dt, ws["mts"], ws["R"], self.d
         L.check(lib.lgen_rmsnorm(L.ptr(ws["hp"]), L.ptr(self.norm_w), L.ptr(ws["xn"]), mts, d, self.eps, dt, st), "rmsnorm")
         lg = torch.empty(mts * 16, self.V, dtype=self.dtype, device=self.dev)
-        self.gemm(self.out_w, ws["xn"], lg, R, mts, self.V, d, L.EPI_ROWS, (min(mts, 4), 1, max(1, min(8, (d // self.kc) // 2))))
+        self.gemm(self.out_w, ws["xn"], lg, R, mts, self.V, d, L.EPI_ROWS, self._sequence_tiles(mts, d))
         return lg
 
     def score_sequence(self, model, cond_combined, ids, B, emb_masks, cfg_scale, temperature):
@@ -553,22 +573,13 @@ class DecodeEngine:
         gpt.py:373-380 does for the cross-entropy).  cond_combined: the B2 = B or 2B conditioning rows of generate() (conditional
         rows, then their unconditional twins); emb_masks: [B2, T] or None."""
         N = ids.shape[1]
-        if model.model_type == "c2i":
-            cond = self.cls_emb[cond_combined.reshape(-1).long()].unsqueeze(1)
-        else:
-            cond = self.caption_embed(cond_combined)
-        cond = cond[:, : self.T]
+        cond = self._cond_rows(model, cond_combined)
         T, B2 = cond.shape[1], cond.shape[0]
-        if T + N > self.S8 or T + N - 1 > self.freqs_cis.shape[0]:
-            raise IndexError(f"{T} + {N} tokens exceed the caches ({self.S8} slots) / RoPE table ({self.freqs_cis.shape[0]} rows)")
+        self._check_capacity(T, N)
         ids = ids.to(device=self.dev, dtype=torch.int32)
         fed = ids[:, :-1].long().repeat(B2 // B, 1)                                 # the twins are fed the same tokens
         emb = torch.cat([cond, self.tok_emb[fed]], dim=1)                           # [B2, T + N - 1, d]
-        if emb_masks is not None:  # generate.py:154-163, as generate_iter folds them
-            cm = self.causal_mask
-            cm[:, :, :T] = cm[:, :, :T] & emb_masks.to(self.dev).ne(0).unsqueeze(1)
-            cm |= torch.eye(self.S8, dtype=torch.bool, device=self.dev)
-            self.use_mask = True
+        self.fold_emb_masks(emb_masks, T)   # as generate_iter folds them
         ws = self._run_sequence(emb)
         lg = self._sequence_logit_rows(ws)
         S = T + N - 1
@@ -628,15 +639,10 @@ class DecodeEngine:
         (llamagen_amd/pipeline.py); the int32 [B, N] result is the generator's return value."""
         N = max_new_tokens
         T = 1 if model.model_type == "c2i" else cond_combined.shape[1]
-        if T + N > self.S8 or T + N - 1 > self.freqs_cis.shape[0]:
-            raise IndexError(f"{T} + {N} tokens exceed the caches ({self.S8} slots) / RoPE table ({self.freqs_cis.shape[0]} rows)")
+        self._check_capacity(T, N)
         self._prof = getattr(model, "_prof", None)
         self.state.zero_()
-        if emb_masks is not None:  # generate.py:154-163: fold emb_masks into causal_mask, force the diagonal
-            cm = self.causal_mask
-            cm[:, :, :T] = cm[:, :, :T] & emb_masks.to(self.dev).ne(0).unsqueeze(1)
-            cm |= torch.eye(self.S8, dtype=torch.bool, device=self.dev)
-            self.use_mask = True
+        self.fold_emb_masks(emb_masks, T)
         noise_seq = sp.pop("_noise_seq", None)
         prefilled = sp.pop("_noise_prefilled", False)  # generate.py drew it batch by batch (chains of several batches)
         sampling = bool(sp["sample_logits"])

@@ -42,6 +42,21 @@ def _null_condition(model, cond):
     return model.cls_embedding.uncond_embedding.to(cond.dtype).expand_as(cond)
 
 
+def _rows_and_caches(model, cond, emb_masks, use_cfg, max_new_tokens):
+    """What reference generate.py:128-163 does before the first forward: the step batch's conditioning rows (with CFG the
+    conditional rows, then their unconditional twins), caches set up for them, and the [B, T] validity masks of the (left-padded)
+    caption tokens doubled alike (the twins see the same pattern).  Returns (rows, masks or None)."""
+    B, prefix = cond.shape[0], 1 if model.model_type == "c2i" else cond.shape[1]
+    rows = torch.cat([cond, _null_condition(model, cond)]) if use_cfg else cond
+    model.setup_caches(max_batch_size=rows.shape[0], max_seq_length=prefix + max_new_tokens,
+                       dtype=model.tok_embeddings.weight.dtype)
+    if emb_masks is None:
+        return rows, None
+    assert emb_masks.shape[0] == B
+    assert emb_masks.shape[-1] == prefix
+    return rows, emb_masks.repeat(2, *([1] * (emb_masks.dim() - 1))) if use_cfg else emb_masks
+
+
 def generate_iter(model, cond, max_new_tokens, emb_masks=None, cfg_scale=1.0, cfg_interval=-1, **sampling_kwargs):
     """Same arguments as generate(); a generator that yields after every enqueued decode step and returns
     the int32 [B, N] ids (StopIteration.value; with return_logprobs=True the pair (ids, fp32 [B, N] log-probabilities)).
@@ -91,15 +106,7 @@ def generate_iter(model, cond, max_new_tokens, emb_masks=None, cfg_scale=1.0, cf
             emb_masks = torch.cat(mask_parts)
         prefilled = bool(sample_logits)
     B = cond.shape[0]
-    rows = torch.cat([cond, _null_condition(model, cond)]) if use_cfg else cond   # CFG: conditional rows, then their twins
-    model.setup_caches(max_batch_size=rows.shape[0], max_seq_length=prefix + max_new_tokens,
-                       dtype=model.tok_embeddings.weight.dtype)
-    masks = None
-    if emb_masks is not None:  # [B, T] validity of the (left-padded) caption tokens; the twins see the same pattern
-        assert emb_masks.shape[0] == B
-        assert emb_masks.shape[-1] == prefix
-        masks = emb_masks.repeat(2, *([1] * (emb_masks.dim() - 1))) if use_cfg else emb_masks
-
+    rows, masks = _rows_and_caches(model, cond, emb_masks, use_cfg, max_new_tokens)
     sp = dict(use_cfg=use_cfg, cfg_scale=float(cfg_scale), cfg_interval=int(cfg_interval),
               temperature=float(temperature), top_k=int(top_k), top_p=float(top_p),
               sample_logits=bool(sample_logits))
@@ -124,14 +131,7 @@ def score(model, cond, ids, emb_masks=None, cfg_scale=1.0, temperature=1.0):
     if ids.dim() != 2 or ids.shape[0] != cond.shape[0] or ids.shape[1] < 1:
         raise ValueError("ids must be [B, N] with one row per conditioning row")
     use_cfg = cfg_scale > 1.0
-    prefix = 1 if kind == "c2i" else cond.shape[1]
-    B = cond.shape[0]
-    rows = torch.cat([cond, _null_condition(model, cond)]) if use_cfg else cond
-    model.setup_caches(max_batch_size=rows.shape[0], max_seq_length=prefix + ids.shape[1], dtype=model.tok_embeddings.weight.dtype)
-    masks = None
-    if emb_masks is not None:
-        assert emb_masks.shape[0] == B and emb_masks.shape[-1] == prefix
-        masks = emb_masks.repeat(2, *([1] * (emb_masks.dim() - 1))) if use_cfg else emb_masks
+    rows, masks = _rows_and_caches(model, cond, emb_masks, use_cfg, ids.shape[1])
     if kind == "c2i":
         rows = rows.to(torch.int32)
-    return model._engine.score_sequence(model, rows, ids, B, masks, cfg_scale, temperature)
+    return model._engine.score_sequence(model, rows, ids, cond.shape[0], masks, cfg_scale, temperature)

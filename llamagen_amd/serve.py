@@ -174,16 +174,12 @@ class _Bucket:
 
 
 class ContinuousBatcher:
-    logp = None   # a subclass that builds its own state without log-probabilities (the CPU stand-ins of tests/) has no buffer
-
     def __init__(self, model, slots: int, max_new_tokens: int, cfg_scale: float = 1.0, cfg_interval: int = -1,
                  temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, sample_logits: bool = True,
                  slot_buckets: Optional[Sequence[int]] = None, shrink_after: int = 8):
         if model.model_type not in ("c2i", "t2i"):
             raise Exception("please check model type")
         dev = model.tok_embeddings.weight.device
-        if dev.type != "cuda":
-            raise RuntimeError("llamagen_amd.serve runs only on an AMD GPU through the HIP library (no CPU fallback)")
         self.model, self.dev = model, dev
         self.num_classes, self.V = int(model.num_classes), int(model.config.vocab_size)
         self.t2i = model.model_type == "t2i"
@@ -227,7 +223,11 @@ class ContinuousBatcher:
     cond = property(lambda self: self.cur.cond)
 
     def _bucket(self, size: int) -> _Bucket:
+        """The bucket of `size` slots, built on first use: the only place the constructor touches the device (the CPU tests of the
+        host logic override it and `_step`)."""
         if size not in self._buckets:
+            if self.dev.type != "cuda":
+                raise RuntimeError("llamagen_amd.serve runs only on an AMD GPU through the HIP library (no CPU fallback)")
             self._buckets[size] = _Bucket(self.model, size, self.use_cfg, self.S8, self._dtype, self.dev)
         return self._buckets[size]
 
@@ -265,10 +265,8 @@ class ContinuousBatcher:
                 if self.noise is not None:
                     self.noise[t].copy_(self.noise[s])
                 self.seq[t].copy_(self.seq[s])
-                if self.logp is not None:
-                    self.logp[t].copy_(self.logp[s])
-                if getattr(self, "params", None) is not None:
-                    self.params[t].copy_(self.params[s])
+                self.logp[t].copy_(self.logp[s])
+                self.params[t].copy_(self.params[s])
                 self.row_step[t:t + 1].copy_(self.row_step[s:s + 1])
                 self.row_step[s] = self.N
                 self._slot_req[t], self._slot_left[t] = self._slot_req[s], self._slot_left[s]
@@ -316,46 +314,43 @@ class ContinuousBatcher:
             # k candidates of ONE request: k queue entries with ids of their own (never handed out), the same conditioning and
             # seed + j; _output() answers under `rid` with the likeliest once the last one is through
             k = int(sampling.best_of)
-            self.__dict__.setdefault("_group", {})[rid] = [None] * k
+            self._group[rid] = [None] * k
             for j in range(k):
                 cid = self._next_id
                 self._next_id += 1
-                self.__dict__.setdefault("_cand", {})[cid] = (rid, j)
-                self.__dict__.setdefault("_req_sampling", {})[cid] = dataclasses.replace(sampling, best_of=1,
+                self._cand[cid] = (rid, j)
+                self._req_sampling[cid] = dataclasses.replace(sampling, best_of=1,
                                                               seed=None if sampling.seed is None else int(sampling.seed) + j)
                 self._queue.append((cid, label, None))
             return rid
         if sampling is not None:   # a side table, not a fourth queue field: the queue entries stay (rid, label, noise)
-            self.__dict__.setdefault("_req_sampling", {})[rid] = sampling
+            self._req_sampling[rid] = sampling
         self._queue.append((rid, label, noise))
         return rid
 
-    def _sampling_of(self, rid: int) -> Optional[SamplingParams]:
+    def _sampling_of(self, rid: int) -> SamplingParams:
         """The request's own values (taken out of the side table), else the constructor's."""
-        own = getattr(self, "_req_sampling", None)
-        sp = own.pop(rid, None) if own else None
-        return sp if sp is not None else getattr(self, "defaults", None)
+        return self._req_sampling.pop(rid, self.defaults)
 
     def _load(self, b: int, rid: int, label, noise):
         """Slot b <- a fresh request: position / step 0, its class label, its noise block and its sampling record (stream-ordered
         writes, no sync)."""
         sp = self._sampling_of(rid)
-        if sp is not None and getattr(self, "params", None) is not None:
-            rec = torch.from_numpy(pack_sampling(sp))
-            if self.params.is_cuda:   # pinned staging: the copy is enqueued, the host does not wait for it
-                rec = rec.pin_memory()
-            self.params[b].copy_(rec, non_blocking=True)
+        rec = torch.from_numpy(pack_sampling(sp))
+        if self.params.is_cuda:   # pinned staging: the copy is enqueued, the host does not wait for it
+            rec = rec.pin_memory()
+        self.params[b].copy_(rec, non_blocking=True)
         if self.noise is not None:
             if noise is not None:
                 self.noise[b].copy_(noise.to(self.dev))
-            elif sp is not None and not sp.sample_logits:
+            elif not sp.sample_logits:
                 pass  # a greedy request reads no noise: nothing drawn, the other requests' draws stay where they were
-            elif sp is not None and sp.seed is not None:   # serve/model_runner.py:620-645: a generator per seeded request
+            elif sp.seed is not None:   # serve/model_runner.py:620-645: a generator per seeded request
                 self.noise[b].exponential_(1.0, generator=torch.Generator(device=self.dev).manual_seed(int(sp.seed)))
             else:
                 self.noise[b].exponential_(1.0)
         if self.t2i:
-            self._load_caption(b, *label, sp=sp)
+            self._load_caption(b, *label, sp)
             self._slot_req[b], self._slot_left[b] = rid, self.N - 1   # the first token was sampled by the prefill
             return
         self.row_pos[b] = 0
@@ -365,12 +360,11 @@ class ContinuousBatcher:
             self.row_pos[self.B + b] = 0
         self._slot_req[b], self._slot_left[b] = rid, self.N
 
-    def _load_caption(self, b: int, cap: torch.Tensor, emb_mask, sp: Optional[SamplingParams] = None):
+    def _load_caption(self, b: int, cap: torch.Tensor, emb_mask, sp: SamplingParams):
         """Per-request prefill of a text-conditional request (generate.py:128-170 for ONE image): caption (+ null caption with
         CFG) through the CaptionEmbedder and all T prefix positions of every layer on the private engine, first image token sampled
         from the slot's noise block with the REQUEST's sampling values (an unguided request of a guided batcher samples its
         conditional row alone), then K/V slots 0..T-1, mask rows, token and counters move into slot b of the step batch."""
-        sp = sp if sp is not None else self.defaults
         e, T, dev = self.eng, self.T, self.dev
         rows = 2 if self.use_cfg else 1
         if self._pe is None:
@@ -380,11 +374,8 @@ class ContinuousBatcher:
         cond = cap.to(device=dev, dtype=e.dtype).unsqueeze(0)
         if self.use_cfg:
             cond = torch.cat([cond, self.model.cls_embedding.uncond_embedding.to(device=dev, dtype=e.dtype).unsqueeze(0)])
-        if emb_mask is not None:  # generate.py:154-163 on the private engine's mask; both rows see the same pattern
-            cm = pe.causal_mask
-            cm[:, :, :T] = cm[:, :, :T] & emb_mask.to(dev).ne(0).view(1, 1, T)
-            cm |= torch.eye(self.S8, dtype=torch.bool, device=dev)
-        pe.use_mask = True
+        pe.fold_emb_masks(None if emb_mask is None else emb_mask[None], T)   # [1, T]: both rows see the same pattern
+        pe.use_mask = True   # also without a mask
         pe._prefill_prefix(pe.caption_embed(cond))
         pe.state[0] = T - 1
         pe.state[1] = 0
@@ -452,7 +443,7 @@ class ContinuousBatcher:
         """(request id, result) of slot b's finished request, called right after the step that wrote its last token was enqueued:
         the tokens, or with `full` a RequestOutput; (None, None) for a best_of candidate whose request still has others running."""
         cid = self._slot_req[b]
-        cand = self.__dict__.get("_cand", {})
+        cand = self._cand
         if cid not in cand and not full:
             return cid, self.seq[b].clone()
         lp = self.logp[b].clone()

@@ -1,66 +1,12 @@
 """Host logic of llamagen_amd.serve.ContinuousBatcher (no GPU): the request queue, slot refill between steps and the
 "a request that entered at step k is complete after step k + N - 1" accounting.  The device step is a stand-in that writes
 token = label * 1000 + step into the slot's sequence, exactly where lgen_sample_rows would."""
-import collections
-import types
-
 import pytest
 import torch
 
-from llamagen_amd.serve import ContinuousBatcher, bucket_ladder, pick_bucket, plan_moves
-
-
-class _Eng:  # the tensors _switch() moves between buckets
-    def __init__(self, rows, S8):
-        self.k_cache = torch.zeros(1, rows, 1, S8, 1)
-        self.v_cache = torch.zeros(1, rows, 1, S8, 1)
-        self.cur_tok = torch.zeros(rows, dtype=torch.int32)
-
-
-class _Batcher(ContinuousBatcher):
-    def __init__(self, slots, N, cfg=True, buckets=None, shrink_after=2):  # the real constructor builds DecodeEngines on the GPU
-        self.slots, self.N, self.use_cfg = slots, N, cfg
-        self.num_classes, self.V, self.t2i, self.T = 1000, 32, False, 1
-        self.dev = torch.device("cpu")
-        self.bucket_sizes = bucket_ladder(slots, buckets)
-        self.shrink_after, self._shrink_wait, self.switches, self._buckets = shrink_after, 0, 0, {}
-        self.cur = self._bucket(self.bucket_sizes[0] if len(self.bucket_sizes) > 1 else slots)
-        self.row_step = torch.full((slots,), N, dtype=torch.int32)
-        self.noise = None
-        self.seq = torch.zeros(slots, N, dtype=torch.int32)
-        self._queue = collections.deque()
-        self._slot_req, self._slot_left = [None] * slots, [0] * slots
-        self._next_id, self.steps_run = 0, 0
-        self.active_per_step, self.bucket_per_step = [], []
-
-    def _bucket(self, size):
-        if size not in self._buckets:
-            rows = 2 * size if self.use_cfg else size
-            self._buckets[size] = types.SimpleNamespace(B=size, B2=rows, eng=_Eng(rows, self.N + 1), graph=None,
-                                                        row_pos=torch.full((rows,), 1, dtype=torch.int32),
-                                                        cond=torch.full((rows,), 1000, dtype=torch.int32))
-        return self._buckets[size]
-
-    def _step(self):
-        live, e = 0, self.eng
-        for b in range(self.B):
-            st = int(self.row_step[b])
-            if st < self.N:  # an occupied slot: what the layer chain (K/V append) and the sampler kernel do for it
-                label = int(self.cond[b])
-                rows = [b] + ([self.B + b] if self.use_cfg else [])
-                for r in rows:
-                    assert int(self.row_pos[r]) == st
-                    # the request's earlier K/V entries are in ITS rows of the current bucket, whatever bucket wrote them
-                    assert e.k_cache[0, r, 0, :st, 0].tolist() == [label * 1000 + p + (0.5 if r != b else 0) for p in range(st)], (b, st)
-                    e.k_cache[0, r, 0, st, 0] = label * 1000 + st + (0.5 if r != b else 0)
-                    assert st == 0 or int(e.cur_tok[r]) == label * 1000 + st - 1
-                    e.cur_tok[r] = label * 1000 + st
-                    self.row_pos[r] += 1
-                self.seq[b, st] = label * 1000 + st
-                self.row_step[b] += 1
-                live += 1
-        self.active_per_step.append(live)
-        self.bucket_per_step.append(self.B)
+from llamagen_amd.gpt import find_multiple
+from llamagen_amd.serve import RECORD_WORDS, ContinuousBatcher, SamplingParams, bucket_ladder, pick_bucket, plan_moves
+from tests.serve_standin import CPU_MODEL, _Batcher  # greedy unless told otherwise; its step asserts every request's K/V history
 
 
 def test_requests_outnumbering_slots_are_all_served_in_full():
@@ -166,3 +112,45 @@ def test_shrinking_relocates_requests_from_high_slots(cfg):
     assert out[a].tolist() == [41000 + s for s in range(7)] and out[b].tolist() == [42000 + s for s in range(7)]
     assert cb.bucket_per_step == [8, 8, 2, 2, 2, 2, 2] and cb.switches == 2
     assert cb.row_step.tolist()[2:] == [7] * 6        # the vacated slots read as empty
+
+
+def test_constructor_state():
+    """The real constructor, reachable on the CPU through the stand-in's `_bucket`: sequence capacity, bucket ladder, the
+    slot-indexed tensors and the defaults record."""
+    cb = _Batcher(slots=8, N=6, cfg=True, greedy=False, buckets=(2, 4))
+    assert cb.S8 == find_multiple(cb.T + 6, 8) == 8 and cb.V == 32 and cb.num_classes == 1000
+    assert cb.bucket_sizes == [2, 4, 8] and cb.cur.B == 2 and cb.use_cfg and cb.B2 == 4
+    assert cb.row_step.tolist() == [6] * 8 and cb.row_step.dtype == torch.int32
+    assert tuple(cb.seq.shape) == (8, 6) and tuple(cb.logp.shape) == (8, 6) and tuple(cb.noise.shape) == (8, 6, 32)
+    assert tuple(cb.params.shape) == (8, RECORD_WORDS) and (cb.seq.dtype, cb.logp.dtype, cb.params.dtype) == (torch.int32, torch.float32, torch.int32)
+    assert cb.defaults == SamplingParams(cfg_scale=4.0, cfg_interval=-1, temperature=1.0, top_k=100, top_p=1.0, sample_logits=True)
+    assert cb._cand == {} and cb._group == {} and cb._req_sampling == {}
+    greedy = _Batcher(slots=8, N=6, cfg=True, greedy=True, buckets=(2, 4))
+    assert greedy.noise is None and greedy.defaults.sample_logits is False
+
+
+def test_a_cpu_model_is_refused_where_the_first_engine_would_be_built():
+    with pytest.raises(RuntimeError, match=r"^llamagen_amd\.serve runs only on an AMD GPU through the HIP library \(no CPU fallback\)$"):
+        ContinuousBatcher(CPU_MODEL, slots=2, max_new_tokens=4)
+
+
+def test_fold_emb_masks_per_row_and_shared():
+    """DecodeEngine.fold_emb_masks on a bare state object: a [B2, T] mask (generate, score) clears each row's own invalid caption
+    columns, the batcher's [1, T] view the same columns of every row; the diagonal stays set and the attention is told to look."""
+    import types
+    from llamagen_amd.engine import DecodeEngine
+    S8, T = 8, 3
+    fresh = lambda: types.SimpleNamespace(causal_mask=torch.tril(torch.ones(S8, S8, dtype=torch.bool)).repeat(2, 1, 1),
+                                          dev=torch.device("cpu"), S8=S8, use_mask=False)
+    masks = torch.tensor([[0, 1, 1], [0, 0, 1]])
+    for m in (masks, masks[1][None]):
+        e = fresh()
+        DecodeEngine.fold_emb_masks(e, m, T)
+        want = fresh().causal_mask
+        for r in range(2):
+            want[r, :, :T] &= m[r % m.shape[0]].bool()
+            want[r] |= torch.eye(S8, dtype=torch.bool)
+        assert torch.equal(e.causal_mask, want) and e.use_mask is True
+    e = fresh()
+    DecodeEngine.fold_emb_masks(e, None, T)
+    assert torch.equal(e.causal_mask, fresh().causal_mask) and e.use_mask is False

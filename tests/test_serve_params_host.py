@@ -1,18 +1,17 @@
 """Per-request sampling parameters of llamagen_amd.serve (no GPU): SamplingParams validation, the 32-byte slot record, submit()'s
 refusals, and the record's life in the slot table -- written at load, moved with a relocating shrink, replaced at refill.  The
 device step is the stand-in of tests/test_serve_host.py (token = label * 1000 + step)."""
-import collections
 import ctypes
+import functools
 import os
 import re
-import types
 
 import numpy as np
 import pytest
-import torch
 
 from llamagen_amd import _lib as L
-from llamagen_amd.serve import RECORD_WORDS, ContinuousBatcher, SamplingParams, bucket_ladder, pack_sampling
+from llamagen_amd.serve import RECORD_WORDS, RequestOutput, SamplingParams, pack_sampling, pick_best
+from tests import serve_standin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -61,52 +60,7 @@ def test_new_symbol_is_declared_and_has_a_signature():
     assert "#define LGEN_ABI_VERSION 10" in txt and L.ABI_VERSION == 10      # additive: the version does not move
 
 
-class _Eng:
-    def __init__(self, rows, S8):
-        self.k_cache = torch.zeros(1, rows, 1, S8, 1)
-        self.v_cache = torch.zeros(1, rows, 1, S8, 1)
-        self.cur_tok = torch.zeros(rows, dtype=torch.int32)
-
-
-class _Batcher(ContinuousBatcher):
-    """tests/test_serve_host.py's stand-in plus what the real constructor adds for per-request sampling."""
-
-    def __init__(self, slots, N, cfg=True, greedy=False, buckets=None, shrink_after=2):
-        self.slots, self.N, self.use_cfg = slots, N, cfg
-        self.num_classes, self.V, self.t2i, self.T = 1000, 32, False, 1
-        self.dev = torch.device("cpu")
-        self.bucket_sizes = bucket_ladder(slots, buckets)
-        self.shrink_after, self._shrink_wait, self.switches, self._buckets = shrink_after, 0, 0, {}
-        self.cur = self._bucket(self.bucket_sizes[0] if len(self.bucket_sizes) > 1 else slots)
-        self.row_step = torch.full((slots,), N, dtype=torch.int32)
-        self.noise = None if greedy else torch.zeros(slots, N, self.V)
-        self.seq = torch.zeros(slots, N, dtype=torch.int32)
-        self.defaults = SamplingParams(cfg_scale=4.0 if cfg else 1.0, top_k=100, sample_logits=not greedy)
-        self.params = torch.zeros(slots, RECORD_WORDS, dtype=torch.int32)
-        self._req_sampling = {}
-        self._queue = collections.deque()
-        self._slot_req, self._slot_left = [None] * slots, [0] * slots
-        self._next_id, self.steps_run = 0, 0
-        self.records_seen = {}     # request id -> the record of its slot at every step it ran
-
-    def _bucket(self, size):
-        if size not in self._buckets:
-            rows = 2 * size if self.use_cfg else size
-            self._buckets[size] = types.SimpleNamespace(B=size, B2=rows, eng=_Eng(rows, self.N + 1), graph=None,
-                                                        row_pos=torch.full((rows,), 1, dtype=torch.int32),
-                                                        cond=torch.full((rows,), 1000, dtype=torch.int32))
-        return self._buckets[size]
-
-    def _step(self):
-        for b in range(self.B):
-            st = int(self.row_step[b])
-            if st < self.N:
-                label = int(self.cond[b])
-                for r in [b] + ([self.B + b] if self.use_cfg else []):
-                    self.row_pos[r] += 1
-                self.seq[b, st] = label * 1000 + st
-                self.row_step[b] += 1
-                self.records_seen.setdefault(self._slot_req[b], []).append((b, self.params[b].tolist()))
+_Batcher = functools.partial(serve_standin._Batcher, greedy=False)   # sampled unless told otherwise; its step records `params`
 
 
 def _words(sp):
@@ -161,11 +115,44 @@ def test_record_follows_a_request_through_a_relocating_shrink():
 
 
 def test_the_stand_in_without_new_attributes_still_takes_sampling():
-    """A batcher object that never ran the real constructor (tests/test_serve_host.py) has neither defaults nor a record table:
-    submit / _load / _switch must tolerate that."""
+    """The greedy stand-in of tests/test_serve_host.py (built by the real constructor like every other: it has defaults and a
+    record table) serves one request that brings sampling values and one that brings none."""
     from tests.test_serve_host import _Batcher as Plain
     cb = Plain(slots=2, N=3)
     rid = cb.submit(7, sampling=SamplingParams(cfg_scale=2.0, sample_logits=False))
     plain = cb.submit(8)
     done = cb.run(use_graph=False)
     assert done[rid].tolist() == [7000, 7001, 7002] and done[plain].tolist() == [8000, 8001, 8002]
+
+
+@pytest.mark.parametrize("plain_first", [False, True])
+@pytest.mark.parametrize("full", [False, True])
+def test_best_of_answers_with_the_likeliest_candidate(full, plain_first):
+    """best_of=3 next to a plain request on 3 slots (the fewest check_best_of admits for three candidates; with the plain request
+    ahead of them the last candidate waits for a refill and finishes after the others): the candidates run as requests of their
+    own (the stand-in step gives candidate j tokens + 100 * (j + 1) and the per-token log-probability chosen here), the answer
+    under the request's id is the one pick_best names, and nothing is left in the candidate tables."""
+    per_token = [-1.0, -0.25, -0.5]
+    cb = _Batcher(slots=3, N=4)
+    with pytest.raises(ValueError):
+        _Batcher(slots=2, N=4).submit(7, sampling=SamplingParams(best_of=3, seed=5))   # a candidate without a slot of its own
+    if plain_first:
+        plain = cb.submit(8)
+    rid = cb.submit(7, sampling=SamplingParams(best_of=3, seed=5))
+    if not plain_first:
+        plain = cb.submit(8)
+    assert sorted(cb._cand.values()) == [(rid, 0), (rid, 1), (rid, 2)] and len(cb._queue) == 4
+    assert sorted(cb._req_sampling[c].seed for c in cb._cand) == [5, 6, 7] and all(cb._req_sampling[c].best_of == 1 for c in cb._cand)
+    for cid, (_, j) in cb._cand.items():
+        cb.marks[cid] = (100 * (j + 1), per_token[j])
+    done = cb.run(use_graph=False, return_outputs=full)
+    win = pick_best([4 * lp for lp in per_token])
+    assert win == 1 and sorted(done) == sorted([rid, plain]) and cb.steps_run == 8
+    want = [7000 + 100 * (win + 1) + s for s in range(4)]
+    if full:
+        assert isinstance(done[rid], RequestOutput) and done[rid].token_ids.tolist() == want
+        assert done[rid].logprobs.tolist() == [per_token[win]] * 4 and done[rid].cumulative_logprob.item() == 4 * per_token[win]
+        assert done[plain].token_ids.tolist() == [8000 + s for s in range(4)] and done[plain].cumulative_logprob.item() == 0.0
+    else:
+        assert done[rid].tolist() == want and done[plain].tolist() == [8000 + s for s in range(4)]
+    assert not cb._cand and not cb._group and not cb._req_sampling and all(r is None for r in cb._slot_req)
