@@ -10,6 +10,8 @@ re-layout only.
 from __future__ import annotations
 
 import os
+from collections import namedtuple
+from functools import partial
 
 import torch
 
@@ -64,6 +66,28 @@ class _Act:
         self.t, self.part, self.ntiles, self.qstride, self.width = t, part, ntiles, qstride, width
 
 
+# The input of the convs that produce one B x H x W map, prepared for the kernel family that will run them: for lgen_conv_fused
+# the activation x with the GroupNorm (scale, shift) and the swish flag it applies on the tile load (planes is None), for
+# lgen_conv_igemm the normalised / activated (hi, lo) bf16 planes.
+_Prep = namedtuple("_Prep", "B H W resample x coef swish planes", defaults=(None, None, False, None))
+
+
+def _res_w(r):
+    return dict(n1=_GNW(r.norm1), c1=_ConvW(r.conv1), n2=_GNW(r.norm2), c2=_ConvW(r.conv2),
+                nin=_ConvW(r.nin_shortcut) if hasattr(r, "nin_shortcut") else None)
+
+
+def _att_w(a):
+    return dict(n=_GNW(a.norm), q=_ConvW(a.q), k=_ConvW(a.k), v=_ConvW(a.v), p=_ConvW(a.proj_out))
+
+
+def _level_w(res, attn, resample=None):
+    """One resolution level: its ResBlocks, the AttnBlock that follows res[i] where there is one, its Upsample / Downsample conv.
+    The mid block (Res, Attn, Res) is such a level too: two ResBlocks, an AttnBlock after the first, no resampling."""
+    return dict(res=[_res_w(r) for r in res], attn=[_att_w(a) for a in attn],
+                conv=_ConvW(resample.conv) if resample is not None else None)
+
+
 class VQEngine:
     def __init__(self, model):
         self.lib = L.lib()
@@ -74,27 +98,16 @@ class VQEngine:
         if os.environ.get("LGEN_CF_VARIANT") is not None:  # tuning knob, see lgen_debug_set_conv_fused_variant in lgen.h
             self.lib.lgen_debug_set_conv_fused_variant(int(os.environ["LGEN_CF_VARIANT"]))
         cfg = model.config
-        self.n_e, self.e_dim, self.l2 = cfg.codebook_size, cfg.codebook_embed_dim, cfg.codebook_l2_norm
+        self.n_e, self.e_dim, self.l2, self.zc = cfg.codebook_size, cfg.codebook_embed_dim, cfg.codebook_l2_norm, cfg.z_channels
         self._sig_v = self._sig(model)
         dec = model.decoder
-        self.num_res = dec.num_resolutions
-        self.nrb = dec.num_res_blocks
-        C = lambda m: _ConvW(m)
-        G = lambda m: _GNW(m)
-        res = lambda r: dict(n1=G(r.norm1), c1=C(r.conv1), n2=G(r.norm2), c2=C(r.conv2),
-                             nin=C(r.nin_shortcut) if hasattr(r, "nin_shortcut") else None)
-        att = lambda a: dict(n=G(a.norm), q=C(a.q), k=C(a.k), v=C(a.v), p=C(a.proj_out))
-        self.conv_in = C(dec.conv_in)
-        self.mid = [res(dec.mid[0]), att(dec.mid[1]), res(dec.mid[2])]
-        self.levels = []
-        for blk in dec.conv_blocks:
-            self.levels.append(dict(res=[res(r) for r in blk.res], attn=[att(a) for a in blk.attn],
-                                    up=C(blk.upsample.conv) if hasattr(blk, "upsample") else None))
-        self.norm_out, self.conv_out = G(dec.norm_out), C(dec.conv_out)
+        self.conv_in = _ConvW(dec.conv_in)
+        self.levels = [_level_w([dec.mid[0], dec.mid[2]], [dec.mid[1]])]
+        self.levels += [_level_w(blk.res, blk.attn, getattr(blk, "upsample", None)) for blk in dec.conv_blocks]
+        self.norm_out, self.conv_out = _GNW(dec.norm_out), _ConvW(dec.conv_out)
         # post_quant_conv 1x1 (Cin = e_dim): handled by the gather kernel
-        self.pq_w = model.post_quant_conv.weight.detach().float().reshape(cfg.z_channels, self.e_dim).contiguous()
+        self.pq_w = model.post_quant_conv.weight.detach().float().reshape(self.zc, self.e_dim).contiguous()
         self.pq_b = model.post_quant_conv.bias.detach().float().contiguous()
-        self.zc = cfg.z_channels
         cb = model.quantize.embedding.weight.detach().float().contiguous()
         self.cbn = torch.empty_like(cb)
         self.esq = torch.empty(self.n_e, device=self.dev)
@@ -105,7 +118,8 @@ class VQEngine:
         self._model_ref = model
         # weight planes / codebook prep were enqueued on the constructing stream; lanes use this engine from their own
         # streams without an event dependency, so finish the one-time setup here
-        torch.cuda.current_stream(self.dev).synchronize()
+        if self.dev.type == "cuda":
+            torch.cuda.current_stream(self.dev).synchronize()
 
     @staticmethod
     def _sig(model):
@@ -132,50 +146,50 @@ class VQEngine:
                                              L.ptr(hi), L.ptr(lo), B, hw, C, mode, L.stream()), "gn_swish_split")
         return hi, lo
 
-    def _conv(self, planes, cw: _ConvW, B, H, W, upsample=False, res=None, out_nchw=False):
-        """H, W = OUTPUT size; upsample: False / True (nearest-2x input) / 2 (stride-2 Downsample conv)."""
-        hi, lo = planes
-        out = torch.empty(B * H * W * cw.cout, dtype=torch.float32, device=self.dev)
-        L.check(self.lib.lgen_conv_igemm(L.ptr(hi), L.ptr(lo), L.ptr(cw.hi), L.ptr(cw.lo), L.ptr(cw.bias), L.ptr(res),
-                                         L.ptr(out), B, H, W, cw.cin, cw.cout, cw.npad, cw.k, int(upsample),
-                                         1 if out_nchw else 0, 0, 1.0, L.stream()), "conv_igemm")
-        return out
-
-    # ---- fused path (lgen_conv_fused): GroupNorm-apply / swish / split on the tile load, statistics in the epilogue --------
     @staticmethod
     def _fusable(H, W):
         return H % 8 == 0 and W >= 8   # tiles are 8 x 16 pixels; a last tile column may be partly outside the map (24-wide maps)
 
-    def _coef(self, x: "_Act", gn: _GNW, B, hw, C):
+    def _coef(self, x: _Act, gn: _GNW, B, hw, C):
         """Per-channel (scale, shift) of GroupNorm `gn` on activation x: from the producer's tile partials when it has them,
         else from a statistics pass."""
         coef = torch.empty(B * C * 2, dtype=torch.float32, device=self.dev)
-        if x.part is not None:
-            L.check(self.lib.lgen_gn_finalize(L.ptr(x.part), 0, L.ptr(gn.gamma), L.ptr(gn.beta), L.ptr(coef), B, C, x.ntiles,
-                                              x.qstride, hw, x.width, gn.eps, L.stream()), "gn_finalize")
-        else:
-            st = self._stats(x.t, B, hw, C, gn.eps)
-            L.check(self.lib.lgen_gn_finalize(0, L.ptr(st), L.ptr(gn.gamma), L.ptr(gn.beta), L.ptr(coef), B, C, 0, 0, hw, 0, gn.eps,
-                                              L.stream()), "gn_finalize")
+        st = self._stats(x.t, B, hw, C, gn.eps) if x.part is None else None  # then x.ntiles, x.qstride and x.width are 0
+        L.check(self.lib.lgen_gn_finalize(L.ptr(x.part), L.ptr(st), L.ptr(gn.gamma), L.ptr(gn.beta), L.ptr(coef), B, C, x.ntiles,
+                                          x.qstride, hw, x.width, gn.eps, L.stream()), "gn_finalize")
         return coef
 
-    def _convf(self, x: "_Act", cw: _ConvW, B, H, W, coef=None, swish=False, upsample=False, res=None, out_nchw=False,
-               want_part=True) -> "_Act":
-        """H, W = OUTPUT size.  x.t is fp32 NHWC [B][H>>ups][W>>ups][cin]."""
+    # ---- conv dispatch: lgen_conv_fused (GroupNorm-apply / swish / split on the tile load, statistics in the epilogue) where the
+    # ---- shape allows it, else a split pass + lgen_conv_igemm; chosen in _prep and nowhere else ---------------------------------
+    def _prep(self, x: _Act, C, B, H, W, gn=None, swish=False, resample=0) -> _Prep:
+        """Prepare x (C channels, optionally through GroupNorm `gn` and swish) as the input of convs with OUTPUT size H x W.
+        resample: 0 none / 1 nearest-2x input / 2 stride-2 Downsample conv, which the fused kernel does not have."""
+        hw = H * W // 4 if resample == 1 else (H * W * 4 if resample == 2 else H * W)  # the INPUT map
+        if self.fused and resample != 2 and self._fusable(H, W):
+            return _Prep(B, H, W, resample, x=x, coef=self._coef(x, gn, B, hw, C) if gn is not None else None, swish=swish)
+        return _Prep(B, H, W, resample, planes=self._split(x.t, B, hw, C, gn, swish))
+
+    def _run(self, pre: _Prep, cw: _ConvW, res: _Act = None, out_nchw=False, want_part=True) -> _Act:
+        """Conv `cw` (+ bias, + res) on a prepared input.  want_part: also write the tile partials of the result for the next
+        GroupNorm -- the fused kernel only; the implicit-GEMM result never carries any."""
+        B, H, W = pre.B, pre.H, pre.W
         out = torch.empty(B * H * W * cw.cout, dtype=torch.float32, device=self.dev)
+        rp = L.ptr(res.t) if res is not None else 0
+        if pre.planes is not None:
+            L.check(self.lib.lgen_conv_igemm(L.ptr(pre.planes[0]), L.ptr(pre.planes[1]), L.ptr(cw.hi), L.ptr(cw.lo), L.ptr(cw.bias),
+                                             rp, L.ptr(out), B, H, W, cw.cin, cw.cout, cw.npad, cw.k, pre.resample,
+                                             1 if out_nchw else 0, 0, 1.0, L.stream()), "conv_igemm")
+            return _Act(out)
         ntiles = (H // 8) * ((W + 15) // 16)
         part = torch.empty(B * ntiles * (cw.fnpad // 4) * 2, dtype=torch.float32, device=self.dev) if want_part else None
-        L.check(self.lib.lgen_conv_fused(L.ptr(x.t), L.ptr(coef), 1 if swish else 0, L.ptr(cw.frag), L.ptr(cw.bias),
-                                         L.ptr(res.t if isinstance(res, _Act) else res), L.ptr(out), L.ptr(part), B, H, W, cw.cin,
-                                         cw.cout, cw.fnpad, cw.k, 1 if upsample else 0, 1 if out_nchw else 0, L.stream()),
-                "conv_fused")
-        return _Act(out, part, ntiles, cw.fnpad // 4, W)
+        L.check(self.lib.lgen_conv_fused(L.ptr(pre.x.t), L.ptr(pre.coef), 1 if pre.swish else 0, L.ptr(cw.frag), L.ptr(cw.bias), rp,
+                                         L.ptr(out), L.ptr(part), B, H, W, cw.cin, cw.cout, cw.fnpad, cw.k, pre.resample,
+                                         1 if out_nchw else 0, L.stream()), "conv_fused")
+        return _Act(out, part, ntiles, cw.fnpad // 4, W) if want_part else _Act(out)
 
-    def _res_fused(self, x: "_Act", p, B, H, W) -> "_Act":
-        hw, cin = H * W, p["c1"].cin
-        h = self._convf(x, p["c1"], B, H, W, coef=self._coef(x, p["n1"], B, hw, cin), swish=True)
-        skip = x if p["nin"] is None else self._convf(x, p["nin"], B, H, W, want_part=False)
-        return self._convf(h, p["c2"], B, H, W, coef=self._coef(h, p["n2"], B, hw, p["c1"].cout), swish=True, res=skip)
+    def _conv(self, x: _Act, cw: _ConvW, B, H, W, gn=None, swish=False, resample=0, **kw) -> _Act:
+        """_prep + _run for an input with one consumer; H, W = OUTPUT size."""
+        return self._run(self._prep(x, cw.cin, B, H, W, gn, swish, resample), cw, **kw)
 
     def _gemm_nt(self, a_planes, b_planes, B, M, N, K, npad, alpha):
         """out[b] = alpha * A[b] (M x K) . Bm[b] (N x K)^T, batched, via the igemm kernel (1x1, W = 1)."""
@@ -185,33 +199,15 @@ class VQEngine:
         return out
 
     # ---- blocks (vq_model.py:299-314, 327-351) ----------------------------------------------
-    def _res(self, x, p, B, H, W):
-        if isinstance(x, _Act):
-            if self.fused and self._fusable(H, W):
-                return self._res_fused(x, p, B, H, W)
-            return _Act(self._res(x.t, p, B, H, W))
-        hw, cin = H * W, p["c1"].cin
-        h = self._conv(self._split(x, B, hw, cin, p["n1"], True), p["c1"], B, H, W)
-        cmid = p["c1"].cout
-        skip = x if p["nin"] is None else self._conv(self._split(x, B, hw, cin), p["nin"], B, H, W)
-        return self._conv(self._split(h, B, hw, cmid, p["n2"], True), p["c2"], B, H, W, res=skip)
+    def _res(self, x: _Act, p, B, H, W) -> _Act:
+        h = self._conv(x, p["c1"], B, H, W, gn=p["n1"], swish=True)
+        skip = x if p["nin"] is None else self._conv(x, p["nin"], B, H, W, want_part=False)
+        return self._run(self._prep(h, p["c1"].cout, B, H, W, p["n2"], True), p["c2"], res=skip)
 
-    def _attn(self, x, p, B, H, W):
-        fused = isinstance(x, _Act) and self.fused and self._fusable(H, W)
-        if isinstance(x, _Act) and not fused:
-            return _Act(self._attn(x.t, p, B, H, W))
+    def _attn(self, x: _Act, p, B, H, W) -> _Act:
         hw, c = H * W, p["q"].cin
-        if fused:  # GroupNorm-apply on the tile load of the three 1x1 convs (no activation, vq_model.py:330-334)
-            coef = self._coef(x, p["n"], B, hw, c)
-            xa, x = x, x.t
-            q = self._convf(xa, p["q"], B, H, W, coef=coef, want_part=False).t
-            k = self._convf(xa, p["k"], B, H, W, coef=coef, want_part=False).t
-            v = self._convf(xa, p["v"], B, H, W, coef=coef, want_part=False).t
-        else:
-            hn = self._split(x, B, hw, c, p["n"], False)
-            q = self._conv(hn, p["q"], B, H, W)
-            k = self._conv(hn, p["k"], B, H, W)
-            v = self._conv(hn, p["v"], B, H, W)
+        hn = self._prep(x, c, B, H, W, gn=p["n"])  # GroupNorm once for the three 1x1 convs (no activation, vq_model.py:330-334)
+        q, k, v = [self._run(hn, p[n], want_part=False).t for n in "qkv"]
         blk = 128 if hw % 128 == 0 else (64 if hw % 64 == 0 else 16)
         npad = (hw + blk - 1) // blk * blk
         ld = (hw + 31) // 32 * 32
@@ -226,9 +222,21 @@ class VQEngine:
         L.check(self.lib.lgen_split_t(L.ptr(v), L.ptr(vh), L.ptr(vl), B, hw, c, ld, L.stream()), "split_t")
         cblk = 128 if c % 128 == 0 else (64 if c % 64 == 0 else 16)
         o = self._gemm_nt((ph, pl), (vh, vl), B, hw, c, ld, (c + cblk - 1) // cblk * cblk, 1.0)
-        if fused:  # proj_out + skip, with the statistics of the result for the next block's norm1
-            return self._convf(_Act(o), p["p"], B, H, W, res=xa)
-        return self._conv(self._split(o, B, hw, c), p["p"], B, H, W, res=x)
+        return self._conv(_Act(o), p["p"], B, H, W, res=x)  # proj_out + skip (fused: with the statistics for the next norm1)
+
+    def _blocks(self, levels, H, W, resample):
+        """The level loop of the decoder (vq_model.py:180-191) and the encoder (:111-122): every block of `levels` in order as
+        (method, weights, H, W of its output), each level's Upsample (resample 1) / Downsample (2) conv included.  The caller runs
+        `x = method(x, weights, B, H, W)` itself: a frame here that held a level's input while its blocks run would keep one more
+        full-resolution map alive at the last decoder level."""
+        for lv in levels:
+            for bi, rp in enumerate(lv["res"]):
+                yield self._res, rp, H, W
+                if bi < len(lv["attn"]):
+                    yield self._attn, lv["attn"][bi], H, W
+            if lv["conv"] is not None:  # Downsample is the stride-2 conv (vq_model.py:389-393): always the implicit-GEMM path
+                H, W = (2 * H, 2 * W) if resample == 1 else (H // 2, W // 2)
+                yield partial(self._conv, resample=resample), lv["conv"], H, W
 
     # ---- public ----------------------------------------------------------------------------------
     def decode_code(self, code_b, shape, channel_first=True):
@@ -241,49 +249,29 @@ class VQEngine:
         idx = code_b.reshape(-1).to(device=self.dev, dtype=torch.int64).contiguous()
         if idx.numel() != B * h * w or C != self.e_dim:
             raise ValueError(f"code_b has {idx.numel()} ids, shape {shape} expects {B * h * w} x {self.e_dim}")
-        z = torch.empty(B * h * w * self.zc, dtype=torch.float32, device=self.dev)
-        L.check(self.lib.lgen_vq_lookup_pqconv(L.ptr(self.cbn), L.ptr(idx), L.ptr(self.pq_w), L.ptr(self.pq_b), L.ptr(z),
-                                               B * h * w, self.n_e, self.e_dim, self.zc, L.stream()), "lookup_pqconv")
-        return self._decoder(z, B, h, w)
+        return self._decoder(self._pqconv(self.cbn, idx, self.n_e, self.e_dim, "lookup_pqconv"), B, h, w)
 
     def decode(self, quant):
         """quant: fp32 [B, e_dim, h, w] (already-quantised latents) -> post_quant_conv -> Decoder."""
         B, C, h, w = quant.shape
         zz = quant.to(self.dev, torch.float32).permute(0, 2, 3, 1).reshape(-1, C).contiguous()  # per-pixel "codebook"
         idx = torch.arange(B * h * w, dtype=torch.int64, device=self.dev)
-        z = torch.empty(B * h * w * self.zc, dtype=torch.float32, device=self.dev)
-        L.check(self.lib.lgen_vq_lookup_pqconv(L.ptr(zz), L.ptr(idx), L.ptr(self.pq_w), L.ptr(self.pq_b), L.ptr(z), B * h * w,
-                                               B * h * w, C, self.zc, L.stream()), "pqconv")
-        return self._decoder(z, B, h, w)
+        return self._decoder(self._pqconv(zz, idx, B * h * w, C, "pqconv"), B, h, w)
 
-    def _decoder(self, z, B, H, W):
+    def _pqconv(self, table, idx, n_e, e_dim, what) -> _Act:
+        """post_quant_conv of rows idx of table [n_e][e_dim] -> NHWC [idx.numel() * z_channels]."""
+        z = torch.empty(idx.numel() * self.zc, dtype=torch.float32, device=self.dev)
+        L.check(self.lib.lgen_vq_lookup_pqconv(L.ptr(table), L.ptr(idx), L.ptr(self.pq_w), L.ptr(self.pq_b), L.ptr(z), idx.numel(),
+                                               n_e, e_dim, self.zc, L.stream()), what)
+        return _Act(z)
+
+    def _decoder(self, z: _Act, B, H, W):
         """Decoder.forward, vq_model.py:173-194; z NHWC [B*H*W*z_channels]."""
-        if self.fused and self._fusable(H, W):
-            x = self._convf(_Act(z), self.conv_in, B, H, W)
-        else:
-            x = _Act(self._conv(self._split(z, B, H * W, self.zc), self.conv_in, B, H, W))
-        x = self._res(x, self.mid[0], B, H, W)
-        x = self._attn(x, self.mid[1], B, H, W)
-        x = self._res(x, self.mid[2], B, H, W)
-        for li, lv in enumerate(self.levels):
-            for bi, rp in enumerate(lv["res"]):
-                x = self._res(x, rp, B, H, W)
-                if lv["attn"]:
-                    x = self._attn(x, lv["attn"][bi], B, H, W)
-            if lv["up"] is not None:
-                c = lv["up"].cin
-                if self.fused and self._fusable(2 * H, 2 * W):
-                    x = self._convf(x, lv["up"], B, 2 * H, 2 * W, upsample=True)
-                else:
-                    x = _Act(self._conv(self._split(x.t, B, H * W, c), lv["up"], B, 2 * H, 2 * W, upsample=True))
-                H, W = 2 * H, 2 * W
-        c = self.conv_out.cin
-        if self.fused and self._fusable(H, W):
-            out = self._convf(x, self.conv_out, B, H, W, coef=self._coef(x, self.norm_out, B, H * W, c), swish=True,
-                              out_nchw=True, want_part=False).t
-        else:
-            out = self._conv(self._split(x.t, B, H * W, c, self.norm_out, True), self.conv_out, B, H, W, out_nchw=True)
-        return out.view(B, self.conv_out.cout, H, W)
+        x = self._conv(z, self.conv_in, B, H, W)
+        for block, p, H, W in self._blocks(self.levels, H, W, 1):  # mid, then the up-sampling levels
+            x = block(x, p, B, H, W)
+        out = self._conv(x, self.conv_out, B, H, W, gn=self.norm_out, swish=True, out_nchw=True, want_part=False)
+        return out.t.view(B, self.conv_out.cout, H, W)
 
     def argmin(self, z):
         """Nearest codebook entry per latent vector (vq_model.py:215-232): z [B, e_dim, h, w] -> int64 [B*h*w]."""
@@ -297,18 +285,10 @@ class VQEngine:
     # ---- encoder (vq_model.py:64-124, 41-45) ----------------------------------------------------------
     def _encoder_weights(self):
         if self._enc is None:
-            model = self._model_ref
-            enc = model.encoder
-            C, G = _ConvW, _GNW
-            res = lambda r: dict(n1=G(r.norm1), c1=C(r.conv1), n2=G(r.norm2), c2=C(r.conv2),
-                                 nin=C(r.nin_shortcut) if hasattr(r, "nin_shortcut") else None)
-            att = lambda a: dict(n=G(a.norm), q=C(a.q), k=C(a.k), v=C(a.v), p=C(a.proj_out))
-            self._enc = dict(
-                conv_in=C(enc.conv_in),
-                levels=[dict(res=[res(r) for r in blk.res], attn=[att(a) for a in blk.attn],
-                             down=C(blk.downsample.conv) if hasattr(blk, "downsample") else None) for blk in enc.conv_blocks],
-                mid=[res(enc.mid[0]), att(enc.mid[1]), res(enc.mid[2])],
-                norm_out=G(enc.norm_out), conv_out=C(enc.conv_out), quant=C(model.quant_conv))
+            model, enc = self._model_ref, self._model_ref.encoder
+            levels = [_level_w(blk.res, blk.attn, getattr(blk, "downsample", None)) for blk in enc.conv_blocks]
+            self._enc = dict(conv_in=_ConvW(enc.conv_in), levels=levels + [_level_w([enc.mid[0], enc.mid[2]], [enc.mid[1]])],
+                             norm_out=_GNW(enc.norm_out), conv_out=_ConvW(enc.conv_out), quant=_ConvW(model.quant_conv))
         return self._enc
 
     def encode(self, x):
@@ -316,37 +296,16 @@ class VQEngine:
         (None, None, indices int64 [B*h*w])) like vq_model.py:41-45 / 254-259 with self.training False."""
         E = self._encoder_weights()
         B, Cx, H, W = x.shape
-        down = len(E["levels"]) - 1
+        down = sum(lv["conv"] is not None for lv in E["levels"])
         if H % (1 << down) or W % (1 << down):
             raise ValueError(f"image size {H}x{W} must be a multiple of {1 << down}")
-        cin = E["conv_in"].cin
-        xp = torch.zeros(B, H, W, cin, dtype=torch.float32, device=self.dev)  # NHWC, RGB padded to one 32-channel K-step
+        xp = torch.zeros(B, H, W, E["conv_in"].cin, dtype=torch.float32, device=self.dev)  # NHWC, RGB padded to one 32-wide K-step
         xp[..., :Cx] = x.to(self.dev, torch.float32).permute(0, 2, 3, 1)
-        fz = lambda hh, ww: self.fused and self._fusable(hh, ww)
-        if fz(H, W):
-            h = self._convf(_Act(xp.reshape(-1)), E["conv_in"], B, H, W)
-        else:
-            h = _Act(self._conv(self._split(xp.reshape(-1), B, H * W, cin), E["conv_in"], B, H, W))
-        for lv in E["levels"]:
-            for bi, rp in enumerate(lv["res"]):
-                h = self._res(h, rp, B, H, W)
-                if lv["attn"]:
-                    h = self._attn(h, lv["attn"][bi], B, H, W)
-            if lv["down"] is not None:  # stride-2 Downsample conv (vq_model.py:389-393): implicit-GEMM path
-                c = lv["down"].cin
-                h = _Act(self._conv(self._split(h.t, B, H * W, c), lv["down"], B, H // 2, W // 2, upsample=2))
-                H, W = H // 2, W // 2
-        h = self._res(h, E["mid"][0], B, H, W)
-        h = self._attn(h, E["mid"][1], B, H, W)
-        h = self._res(h, E["mid"][2], B, H, W)
-        c = E["conv_out"].cin
-        zc = E["quant"].cin
-        if fz(H, W):
-            h = self._convf(h, E["conv_out"], B, H, W, coef=self._coef(h, E["norm_out"], B, H * W, c), swish=True, want_part=False)
-            z = self._convf(h, E["quant"], B, H, W, out_nchw=True, want_part=False).t.view(B, self.e_dim, H, W)
-        else:
-            h = self._conv(self._split(h.t, B, H * W, c, E["norm_out"], True), E["conv_out"], B, H, W)
-            z = self._conv(self._split(h, B, H * W, zc), E["quant"], B, H, W, out_nchw=True).view(B, self.e_dim, H, W)
+        h = self._conv(_Act(xp.reshape(-1)), E["conv_in"], B, H, W)
+        for block, p, H, W in self._blocks(E["levels"], H, W, 2):  # the down-sampling levels, then mid
+            h = block(h, p, B, H, W)
+        h = self._conv(h, E["conv_out"], B, H, W, gn=E["norm_out"], swish=True, want_part=False)
+        z = self._conv(h, E["quant"], B, H, W, out_nchw=True, want_part=False).t.view(B, self.e_dim, H, W)
         idx = self.argmin(z)
         emb = self.cbn if self.l2 else self._cb
         quant = emb[idx].view(B, H, W, self.e_dim).permute(0, 3, 1, 2).contiguous()  # gather of codebook rows (no arithmetic)

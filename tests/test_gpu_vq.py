@@ -416,7 +416,9 @@ def test_fused_groupnorm_statistics_survive_a_large_offset():
 
 def test_decode_code_fused_matches_unfused(monkeypatch):
     """The fused decoder path (default) and the round-1 path (LGEN_VQ_FUSED=0: gn_stats + gn_swish_split + conv_igemm) agree to
-    fp32 rounding on a 128 px image (both paths in use: the 8x8 level is un-fusable, the 16 .. 128 px levels fused)."""
+    fp32 rounding on a 128 px image.  At an 8x8 grid every level, 8x8 included, is fused in the default mode, and the un-fused run
+    is all implicit-GEMM; sequences that mix the two are covered by the golden tests of vq16_3x5 and enc16_48x32 and by the launch
+    traces of tests/test_vq_engine_host.py."""
     case = VQ_CASES["vq16_4x4"]
     m, sd = build_vq_holder(case)
     dev = _dev()
