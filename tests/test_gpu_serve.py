@@ -22,11 +22,11 @@ def _model(dtype):
     return m.to(device=torch.device("cuda:0"), dtype=dtype).eval(), sd
 
 
-@pytest.mark.parametrize("cfg_scale,slots,use_graph", [(4.0, 3, True), (1.0, 2, True), (3.0, 5, False)])
+@pytest.mark.parametrize("cfg_scale,slots,use_graph", [(4.0, 3, True), (1.0, 2, True), (3.0, 5, False), (4.0, 10, True)])
 def test_requests_are_independent_of_neighbours(cfg_scale, slots, use_graph):
     from llamagen_amd.serve import ContinuousBatcher
     m, sd = _model(torch.float32)
-    N, V, nreq = 16, KW["vocab_size"], 8
+    N, V, nreq = 16, KW["vocab_size"], 14 if slots == 10 else 8   # 10 slots: 20 paired rows on two m-tiles, refilled by 4 more requests
     g = torch.Generator().manual_seed(11)
     labels = torch.randint(0, 10, (nreq,), generator=g).tolist()
     noises = [torch.empty(N, V).exponential_(1, generator=g) for _ in range(nreq)]
