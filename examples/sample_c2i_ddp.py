@@ -40,6 +40,8 @@ def build_parser():
     p.add_argument("--cls-token-num", type=int, default=1, help="max token number of condition input")
     p.add_argument("--precision", type=str, default="bf16", choices=["none", "fp16", "bf16"])
     p.add_argument("--compile", action="store_true", default=True)
+    p.add_argument("--kv-cache-dtype", type=str, choices=["auto", "fp8_e4m3"], default="auto",
+                   help="auto: K/V in the storage dtype; fp8_e4m3: 8-bit KV cache (bf16 storage, head_dim <= 64; unit scales)")
     p.add_argument("--vq-model", type=str, choices=list(VQ_models.keys()), default="VQ-16")
     p.add_argument("--vq-ckpt", type=str, default=None, help="ckpt path for vq model")
     p.add_argument("--codebook-size", type=int, default=16384, help="codebook size for vector quantization")
@@ -84,6 +86,8 @@ def main(args):
                                            cls_token_num=args.cls_token_num, model_type=args.gpt_type).to(device=dev, dtype=precision)
     load_gpt_checkpoint(gpt_model, args.gpt_ckpt, from_fsdp=args.from_fsdp)
     gpt_model.eval()
+    if args.kv_cache_dtype != "auto":
+        gpt_model.set_kv_cache(args.kv_cache_dtype)
 
     ckpt_name = args.gpt_ckpt.split("/")[-2] if args.from_fsdp else os.path.basename(args.gpt_ckpt).replace(".pth", "").replace(".pt", "")
     folder = (f"{args.gpt_model.replace('/', '-')}-{ckpt_name}-size-{args.image_size}-size-{args.image_size_eval}-{args.vq_model}-"

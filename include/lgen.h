@@ -15,7 +15,8 @@
  * lgen_conv_wino (the Winograd experiment of round 5 left the product library: tools/experiments/conv_wino/); ABI v10 = v9 +
  * lgen_ssq_group4 (row statistics pre-grouped for the fused-norm consumers) and key-row stride checks in the prefill entry points;
  * v10 + lgen_sample_rows_params is additive (a new symbol, nothing else changes), so the version number stays 10; so are
- * lgen_sample_logprob, lgen_sample_rows_params_logprob and lgen_logprob_rows (per-token log-probabilities).  Each entry point
+ * lgen_sample_logprob, lgen_sample_rows_params_logprob and lgen_logprob_rows (per-token log-probabilities), and the three *_kv8
+ * entry points of the opt-in FP8 KV cache.  Each entry point
  * cites the reference op sequence it replaces (paths relative to the reference repository root).
  *
  * Fragment-packed layouts ("chunk" = 1 KiB = [16 rows][KC k] in MFMA operand order, lane =
@@ -146,6 +147,42 @@ int lgen_gemm_qkv_rope_tile(const void* wp, const void* xp, void* q_out, void* k
 int lgen_attn_decode(const void* q, const void* k_cache, const void* v_cache, void* out_packed, const int* pos_ptr,
                      const unsigned char* mask, int mask_len, int B2, int MTs, int n_head, int hd, int hdp, int S8,
                      int kv_row_stride, int dtype, int variant, void* stream);
+
+/* ---- FP8 KV cache (opt-in; bf16 storage, hdp = 64, one position for all rows) ----------------------------------------
+ * Format: OCP e4m3fn, gfx950's native fp8 -- NOT the fnuz encoding of gfx942.  A cache element is
+ *     q = rne_e4m3(clamp(x_bf16 * inv_s, -448, 448)),      dequantised x^ = float(q) * s,
+ * where x_bf16 is the value the bf16 entry point would have stored (after the storage rounding, after RoPE for K), inv_s =
+ * float32(1 / s) is computed by the HOST and the multiply is one fp32 multiply.  The clamp is explicit, so the stored code never
+ * depends on the conversion's overflow mode (a NaN stays NaN).  One (s_k, s_v) pair per layer, passed per launch.
+ * Layout: the slabs are BYTES, [B2][H][S8] rows of hd valid elements, kv_row_stride BYTES apart (a multiple of 8, >= hd rounded up to
+ * 8; the engine uses hd rounded up to 16), zero-initialised (a zero byte is +0.0: slots never written stay finite) and followed by
+ * >= 64 readable bytes (the attention reads 64 bytes per key whatever the stride, exactly like the bf16 slack rule above).
+ * q, the activations and every other operand stay bf16; q_out of the two append entry points is bit-identical to their bf16 twins.
+ * LGEN_ERR_UNSUPPORTED: dtype != LGEN_BF16 or hdp != 64 (GPT-3B's head_dim 100), lgen_attn_decode_kv8 also for a variant other
+ * than -1, 2, 10.  There is no per-row-position (continuous batching) and no prefill form. */
+
+/* lgen_gemm_qkv_rope with the K / V append quantised as above: k_inv_scale = 1 / s_k, v_inv_scale = 1 / s_v of this layer.  Four
+ * elements per lane = two v_cvt_pk_fp8_f32 into one dword, one vector dword store. */
+int lgen_gemm_qkv_rope_kv8(const void* wp, const void* xp, void* q_out, void* k_cache, void* v_cache, const float* freqs,
+                           const int* pos_ptr, int M, int MTs, int d, int n_head, int hd, int hdp, int S8,
+                           int kv_row_stride, int dtype, int mt, int nt, int kw, const void* norm_w, const float* ssq_in,
+                           int ssq_parts, float eps, int passes, float k_inv_scale, float v_inv_scale, void* stream);
+
+/* lgen_gemm_qkv_rope_tile likewise (the same shapes have an instantiation; LGEN_ERR_UNSUPPORTED as there, nothing is written). */
+int lgen_gemm_qkv_rope_tile_kv8(const void* wp, const void* xp, void* q_out, void* k_cache, void* v_cache, const float* freqs,
+                                const int* pos_ptr, int M, int MTs, int d, int n_head, int hd, int hdp, int S8,
+                                int kv_row_stride, int dtype, int wm, int wn, int mtv, int ntv, int kb, int stages, int lw,
+                                const void* norm_w, const float* ssq_in, int ssq_parts, float eps, float k_inv_scale,
+                                float v_inv_scale, void* stream);
+
+/* lgen_attn_decode on fp8 slabs: variant -1 (2 below 256 rows, 10 from 256 rows), 2 (workgroup form) or 10 (persistent form).
+ * 8 lanes per key with 8-byte non-temporal loads and twice the bf16 variant's loads per group (the same bytes in flight per wave).
+ * K and V unpack to fp32 exactly and a bf16 x e4m3 product is exact in fp32, so the result differs from the bf16 kernels' math on
+ * the dequantised values by summation order only; k_scale = s_k is folded into the one scale per key (sf^2 * s_k), v_scale = s_v
+ * into the final acc / l. */
+int lgen_attn_decode_kv8(const void* q, const void* k_cache, const void* v_cache, void* out_packed, const int* pos_ptr,
+                         const unsigned char* mask, int mask_len, int B2, int MTs, int n_head, int hd, int hdp, int S8,
+                         int kv_row_stride, int dtype, int variant, float k_scale, float v_scale, void* stream);
 
 /* ---- sequence prefill (t2i prefix: all T = cls_token_num caption positions of all B2 rows per layer at once; rows
  * r = t * B2 + b of the packed activations; generate.py:77-86 + gpt.py:348-349 with emb_masks folded into

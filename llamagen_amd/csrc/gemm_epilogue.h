@@ -4,7 +4,10 @@
 #include "lgen_common.h"
 #include "../../include/lgen.h"
 
-enum { EPI_ROWS = 0, EPI_PACKED = 1, EPI_GELU = 2, EPI_RES = 3, EPI_SWIGLU = 4, EPI_QKV = 5 };
+enum { EPI_ROWS = 0, EPI_PACKED = 1, EPI_GELU = 2, EPI_RES = 3, EPI_SWIGLU = 4, EPI_QKV = 5,
+       EPI_QKV8 = 6 };  // EPI_QKV with K/V appended to an fp8 (e4m3) byte slab (lgen_gemm_qkv_rope_kv8); bf16 storage only
+// the two QKV epilogues share everything but the K/V store: a compile-time kind, so that the bf16 instantiations do not change
+constexpr bool epi_qkv(int epi) { return epi == EPI_QKV || epi == EPI_QKV8; }
 
 struct GemmArgs {
     const uint4* wp;     // packed weights [N/16][KCH][64] x 16 B
@@ -15,6 +18,9 @@ struct GemmArgs {
     const float* freqs;  // QKV: [P][hd/2][2] fp32 (cos, sin)
     const int* pos_ptr;  // QKV: position of this token: device scalar, or one per row (pos_stride = 1)
     int pos_stride;      // QKV: 0 = all rows at *pos_ptr; 1 = row m at pos_ptr[m] (continuous batching: every row its own position)
+    float k_inv;         // QKV8: 1 / scale of this layer's K (fp32, computed by the host); kvs is in BYTES there.  (k_inv and v_inv
+                         // sit in what used to be the struct's two padding words: sizeof(GemmArgs), and with it the kernel-argument
+                         // layout of every existing instantiation, is unchanged)
     const uint4* nw;     // NORM: RMSNorm weight [K] storage dtype
     const float* ssq_in; // NORM: [MTs*16][LGEN_SSQ_STRIDE], `parts` partial sums of squares per x row
     float* ssq_out;      // RES: [MTs*16][LGEN_SSQ_STRIDE], N/16 partials per new row (nullable)
@@ -25,7 +31,9 @@ struct GemmArgs {
     float eps, inv_k;
     int passes;          // fused-norm GEMMs: consecutive n-groups one workgroup walks with its activations kept in registers (>= 1)
     int db;              // gemm_tile.hip: development ablation mask (LGEN_TILE_ABLATE), 0 in production
+    float v_inv;         // QKV8: 1 / scale of this layer's V
 };
+static_assert(sizeof(GemmArgs) == 152, "GemmArgs grew: every GEMM kernel's argument layout (and ISA) changes with it");
 // weight chunk load: default cache policy (chains in flight share the weights through the memory-side cache; measured better than
 // non-temporal).  One plain load, NOT a run-time choice of policy: a branch per load makes the compiler lose count of the loads in
 // flight and wait for all of them (s_waitcnt vmcnt(0)) in front of the first MFMA, which turns the operand ring into load-all /
@@ -117,7 +125,7 @@ template <int MT, int EPI>
 LGEN_DEV void load_row_pos(const GemmArgs& a, int mt0, int lane, int (&posr)[MT]) {
 #pragma unroll
     for (int i = 0; i < MT; ++i) posr[i] = 0;
-    if constexpr (EPI == 5 /* EPI_QKV */) {
+    if constexpr (epi_qkv(EPI)) {
         if (a.pos_stride) {
 #pragma unroll
             for (int i = 0; i < MT; ++i) posr[i] = a.pos_ptr[(mt0 + i) * 16 + (lane & 15)];
@@ -157,7 +165,7 @@ LGEN_DEV uint4 epi_prefetch(const GemmArgs& a, int nt, int mt, int lane, int pos
         } else {
             aux = *(const uint4*)((const float*)a.out + o);
         }
-    } else if constexpr (EPI == EPI_QKV) {
+    } else if constexpr (epi_qkv(EPI)) {
         const int sec = n / a.d;
         if (sec < 2) {
             const int c = n - sec * a.d;
@@ -203,7 +211,7 @@ LGEN_DEV void epilogue(const GemmArgs& a, int nt, int mt, int lane, f32x4_t v, f
         int f = (nt >> 1) * 16 + g * 4;
         D::st4(a.out, D::xp_off(f, mt, r, a.MTs),
                D::rnd(silu_f(x0)) * y0, D::rnd(silu_f(x1)) * y1, D::rnd(silu_f(x2)) * y2, D::rnd(silu_f(x3)) * y3);
-    } else if constexpr (EPI == EPI_QKV) {
+    } else if constexpr (epi_qkv(EPI)) {
         if (m >= a.M) return;
         const int sec = n / a.d;
         const int c = n - sec * a.d;
@@ -222,13 +230,24 @@ LGEN_DEV void epilogue(const GemmArgs& a, int nt, int mt, int lane, f32x4_t v, f
         void* const pv = a.vc;
         const int hdp = a.hdp, kvs = a.kvs;
         const size_t rh = (size_t)m * a.H + head;
-        void* const dst = sec == 0 ? po : (sec == 1 ? pk : pv);
-        const size_t off = sec == 0 ? rh * hdp + dd : (rh * a.S8 + pos) * kvs + dd;
-        D::st4(dst, off, x0, x1, x2, x3);
+        if constexpr (EPI == EPI_QKV8) {
+            // q as in EPI_QKV (the same bits); K / V: the storage rounding the bf16 path applies at its store, then four e4m3 codes
+            // in one dword, one plain vector store (kvs and the offset are in bytes, dd % 4 == 0)
+            if (sec == 0) {
+                D::st4(po, rh * hdp + dd, x0, x1, x2, x3);
+            } else {
+                const uint32_t w = kv8_quant4(D::rnd(x0), D::rnd(x1), D::rnd(x2), D::rnd(x3), sec == 1 ? a.k_inv : a.v_inv);
+                *(uint32_t*)((unsigned char*)(sec == 1 ? pk : pv) + (rh * a.S8 + pos) * kvs + dd) = w;
+            }
+        } else {
+            void* const dst = sec == 0 ? po : (sec == 1 ? pk : pv);
+            const size_t off = sec == 0 ? rh * hdp + dd : (rh * a.S8 + pos) * kvs + dd;
+            D::st4(dst, off, x0, x1, x2, x3);
+        }
     }
 }
 
-template <int EPI> constexpr bool epi_has_aux() { return EPI == EPI_RES || EPI == EPI_QKV; }
+template <int EPI> constexpr bool epi_has_aux() { return EPI == EPI_RES || epi_qkv(EPI); }
 
 
 // ---- what every K-splitting GEMM kernel does around its MFMA loop (gemm_kernel, gemm_steady_kernel, np_pass) ----------------

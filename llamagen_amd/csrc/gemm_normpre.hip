@@ -133,13 +133,13 @@ template <int MT, int NT, int EPI, int CPW, int MODE>
 constexpr bool np_spills() {
     if (MODE > 0) {
         if (!((MT == 1 && NT == 4) || (MT == 2 && NT == 2) || (MT == 2 && NT == 4) || (MT == 4 && NT == 2))) return true;
-        if (MT == 4 && (EPI == EPI_QKV || CPW >= 5)) return true;
-        if (MT == 2 && NT == 4 && EPI == EPI_QKV && CPW >= 5) return true;
+        if (MT == 4 && (epi_qkv(EPI) || CPW >= 5)) return true;
+        if (MT == 2 && NT == 4 && epi_qkv(EPI) && CPW >= 5) return true;
         return false;
     }
-    if (MT == 2 && NT == 1 && EPI == EPI_QKV) return true;  // 40 B of scratch; a tuning-only shape (fused qkv runs nt = 4)
-    return (MT == 4 && CPW == 6) || (MT == 4 && NT == 4 && CPW == 5) || (MT == 4 && NT >= 2 && EPI == EPI_QKV && CPW >= 5) ||
-           (MT == 4 && NT == 4 && EPI == EPI_QKV) || (MT == 2 && NT == 4 && EPI == EPI_QKV && CPW == 6);
+    if (MT == 2 && NT == 1 && epi_qkv(EPI)) return true;  // 40 B of scratch; a tuning-only shape (fused qkv runs nt = 4)
+    return (MT == 4 && CPW == 6) || (MT == 4 && NT == 4 && CPW == 5) || (MT == 4 && NT >= 2 && epi_qkv(EPI) && CPW >= 5) ||
+           (MT == 4 && NT == 4 && epi_qkv(EPI)) || (MT == 2 && NT == 4 && epi_qkv(EPI) && CPW == 6);
 }
 
 template <int MT, int NT, int EPI, int CPW, int MODE>
@@ -204,6 +204,7 @@ int lgen_gemm_normpre_try(const GemmArgs& a, int epi, int dtype, int mt, int nt,
     const int cpw = a.KCH / kw;
     switch (epi) {
         case EPI_QKV: return dispatch_tiles<EPI_QKV>(a, mt, nt, kw, cpw, st);
+        case EPI_QKV8: return dispatch_tiles<EPI_QKV8>(a, mt, nt, kw, cpw, st);
         case EPI_SWIGLU: return dispatch_tiles<EPI_SWIGLU>(a, mt, nt, kw, cpw, st);
         case EPI_ROWS: return dispatch_tiles<EPI_ROWS>(a, mt, nt, kw, cpw, st);
         default: return LGEN_ERR_UNSUPPORTED;

@@ -35,7 +35,7 @@
 // spills; <= 120 registers -> 16 waves (1024 threads) may share a CU's SIMDs, else 8 waves.
 template <int MT, int NT, bool NORM, int EPI>
 constexpr int gemm_fixed_regs() {
-    return NT * MT * 4 + (epi_has_aux<EPI>() ? NT * MT * 4 : 0) + (NORM ? 44 : 0) + (EPI == EPI_QKV ? 16 : 0) + 36;
+    return NT * MT * 4 + (epi_has_aux<EPI>() ? NT * MT * 4 : 0) + (NORM ? 44 : 0) + (epi_qkv(EPI) ? 16 : 0) + 36;
 }
 template <int MT, int NT, bool NORM, int EPI>
 constexpr int gemm_depth() {
@@ -139,7 +139,7 @@ __global__ __launch_bounds__((gemm_max_threads<MT, NT, NORM, EPI>())) void gemm_
 
 // ring-buffer shapes whose operand set does not fit 256 VGPRs (they would spill; csrc/gemm_skinny.usage): refused, not compiled
 template <int MT, int NT, int EPI, bool NORM>
-constexpr bool gemm_spills() { return NORM && (MT == 8 || (MT == 4 && NT == 4 && EPI == EPI_QKV)); }
+constexpr bool gemm_spills() { return NORM && (MT == 8 || (MT == 4 && NT == 4 && epi_qkv(EPI))); }
 
 // ---- steady-state form for wide models (round 3) ---------------------------------------------------------------------
 // Same operation, same wave partition and the same chunk order per wave as gemm_kernel<..., NORM = false> -- bit-identical
@@ -224,7 +224,7 @@ __global__ __launch_bounds__((gemm_max_threads<MT, NT, false, EPI>())) void gemm
 template <typename D, int MT, int NT, int EPI, bool NORM>
 constexpr bool gemm_has_steady() {
     if (!std::is_same<D, BF16>::value || NORM) return false;
-    return (EPI == EPI_RES || EPI == EPI_SWIGLU || EPI == EPI_QKV || EPI == EPI_ROWS) &&
+    return (EPI == EPI_RES || EPI == EPI_SWIGLU || epi_qkv(EPI) || EPI == EPI_ROWS) &&
            ((MT == 4 && (NT == 1 || NT == 2 || NT == 4)) || (MT == 2 && (NT == 2 || NT == 4)) || (MT == 8 && (NT == 1 || NT == 2)));
 }
 
@@ -294,14 +294,18 @@ static int dispatch(const GemmArgs& a, int mt, int nt, int kw, hipStream_t st) {
 
 template <int EPI, bool NORM>
 static int dispatch_dt(const GemmArgs& a, int dtype, int mt, int nt, int kw, hipStream_t st) {
-    return lgen_dispatch_dtype(dtype, [&](auto tag) { return dispatch<decltype(tag), EPI, NORM>(a, mt, nt, kw, st); });
+    if constexpr (EPI == EPI_QKV8) {   // the fp8 KV append exists for bf16 storage alone
+        return dtype == LGEN_BF16 ? dispatch<BF16, EPI, NORM>(a, mt, nt, kw, st) : LGEN_ERR_UNSUPPORTED;
+    } else {
+        return lgen_dispatch_dtype(dtype, [&](auto tag) { return dispatch<decltype(tag), EPI, NORM>(a, mt, nt, kw, st); });
+    }
 }
 
 // RMSNorm-prologue variants exist for the three consumers of a normalised residual stream
 template <int EPI>
 static int dispatch_norm(const GemmArgs& a, int dtype, int mt, int nt, int kw, hipStream_t st) {
     if (a.nw) {
-        if constexpr (EPI == EPI_QKV || EPI == EPI_SWIGLU || EPI == EPI_ROWS) {
+        if constexpr (epi_qkv(EPI) || EPI == EPI_SWIGLU || EPI == EPI_ROWS) {
             if (!a.ssq_in || a.parts < 1) return LGEN_ERR_BAD_ARG;
             const int rc = lgen_gemm_normpre_try(a, EPI, dtype, mt, nt, kw, st);
             if (rc != LGEN_ERR_UNSUPPORTED) return rc;
@@ -352,8 +356,9 @@ extern "C" int lgen_gemm(const void* wp, const void* xp, void* out, int M, int M
 static int qkv_rope_impl(const void* wp, const void* xp, void* q_out, void* k_cache, void* v_cache, const float* freqs,
                          const int* pos_ptr, int pos_stride, int M, int MTs, int d, int n_head, int hd, int hdp, int S8,
                          int kv_row_stride, int dtype, int mt, int nt, int kw, const void* norm_w, const float* ssq_in,
-                         int ssq_parts, float eps, int passes, void* stream) {
+                         int ssq_parts, float eps, int passes, void* stream, bool kv8 = false, float k_inv = 1.f, float v_inv = 1.f) {
     const int kcsz = kc_of(dtype);
+    if (kv8 && (dtype != LGEN_BF16 || hdp != 64)) return LGEN_ERR_UNSUPPORTED;
     if (d % kcsz || (3 * d) % 16 || hd % 4 || d != n_head * hd || M > MTs * 16 || pos_stride < 0 || pos_stride > 1 || passes < 1 ||
         passes > 64)
         return LGEN_ERR_BAD_ARG;
@@ -364,12 +369,15 @@ static int qkv_rope_impl(const void* wp, const void* xp, void* q_out, void* k_ca
     a.N = 3 * d; a.KCH = d / kcsz; a.MTs = MTs; a.M = M;
     a.d = d; a.hd = hd; a.hdp = hdp; a.H = n_head; a.S8 = S8;
     a.kvs = kv_row_stride > 0 ? kv_row_stride : hdp;
+    a.k_inv = k_inv; a.v_inv = v_inv;
     {   // rows may be packed tighter than the lane group hdp (lgen.h): at least hd rounded up to one 16-byte piece of the storage type
+        // (fp8 slabs: the stride is in bytes and the piece the attention loads is 8 bytes = 8 elements)
         const int epl_ = epl_of(dtype);
         if (a.kvs < (hd + epl_ - 1) / epl_ * epl_ || a.kvs % epl_) return LGEN_ERR_BAD_ARG;
     }
     a.nw = (const uint4*)norm_w; a.ssq_in = ssq_in; a.parts = ssq_parts; a.eps = eps; a.inv_k = 1.0f / (float)d;
     a.passes = passes;
+    if (kv8) return dispatch_norm<EPI_QKV8>(a, dtype, mt, nt, kw, (hipStream_t)stream);
     return dispatch_norm<EPI_QKV>(a, dtype, mt, nt, kw, (hipStream_t)stream);
 }
 
@@ -387,4 +395,13 @@ extern "C" int lgen_gemm_qkv_rope_rows(const void* wp, const void* xp, void* q_o
                                        const void* norm_w, const float* ssq_in, int ssq_parts, float eps, int passes, void* stream) {
     return qkv_rope_impl(wp, xp, q_out, k_cache, v_cache, freqs, row_pos, 1, M, MTs, d, n_head, hd, hdp, S8, kv_row_stride, dtype,
                          mt, nt, kw, norm_w, ssq_in, ssq_parts, eps, passes, stream);
+}
+
+extern "C" int lgen_gemm_qkv_rope_kv8(const void* wp, const void* xp, void* q_out, void* k_cache, void* v_cache,
+                                      const float* freqs, const int* pos_ptr, int M, int MTs, int d, int n_head, int hd,
+                                      int hdp, int S8, int kv_row_stride, int dtype, int mt, int nt, int kw,
+                                      const void* norm_w, const float* ssq_in, int ssq_parts, float eps, int passes,
+                                      float k_inv_scale, float v_inv_scale, void* stream) {
+    return qkv_rope_impl(wp, xp, q_out, k_cache, v_cache, freqs, pos_ptr, 0, M, MTs, d, n_head, hd, hdp, S8, kv_row_stride, dtype,
+                         mt, nt, kw, norm_w, ssq_in, ssq_parts, eps, passes, stream, true, k_inv_scale, v_inv_scale);
 }

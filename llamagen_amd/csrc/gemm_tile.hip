@@ -205,9 +205,9 @@ __global__ __launch_bounds__(64 * (WM * WN + LW)) void gemm_tile_kernel(GemmArgs
     // ================= consumer wave (LW == 0: also issues its share of the DMA) =================
     // ---- epilogue operands first (oldest requests: they never disturb the counted waits below) ----
     int pos = 0;
-    if constexpr (EPI == EPI_QKV) pos = *a.pos_ptr;   // per-row positions (continuous batching) stay on the skinny kernels
+    if constexpr (epi_qkv(EPI)) pos = *a.pos_ptr;   // per-row positions (continuous batching) stay on the skinny kernels
     uint2 res[NTV][MTV];
-    uint4 rope[EPI == EPI_QKV ? NTV : 1];
+    uint4 rope[epi_qkv(EPI) ? NTV : 1];
     if constexpr (EPI == EPI_RES) {
 #pragma unroll
         for (int j = 0; j < NTV; ++j)
@@ -219,18 +219,18 @@ __global__ __launch_bounds__(64 * (WM * WN + LW)) void gemm_tile_kernel(GemmArgs
     }
     // (wave tiles of >= 20 MFMA tiles -- the 128 x 160 shape of GPT-3B's wqkv -- request the RoPE factors in the epilogue instead,
     // where the operand fragments are dead: 40 more registers across the K loop spill at 256)
-    constexpr bool ROPE_LATE = EPI == EPI_QKV && MTV * NTV >= 20;
+    constexpr bool ROPE_LATE = epi_qkv(EPI) && MTV * NTV >= 20;
     auto load_rope = [&]() {
         QkvCol qc;
         qc.init((ntw0 < ntiles ? ntw0 : ntiles - 1) * 16 + (lane >> 4) * 4, a.d, a.hd);
 #pragma unroll
-        for (int j = 0; j < (EPI == EPI_QKV ? NTV : 1); ++j) {
+        for (int j = 0; j < (epi_qkv(EPI) ? NTV : 1); ++j) {
             rope[j] = make_uint4(0, 0, 0, 0);
             if (qc.sec < 2) rope[j] = *(const uint4*)(a.freqs + ((size_t)pos * (a.hd >> 1) + (qc.dd >> 1)) * 2);
             qc.next16(a.hd, a.H);
         }
     };
-    if constexpr (EPI == EPI_QKV && !ROPE_LATE) load_rope();
+    if constexpr (epi_qkv(EPI) && !ROPE_LATE) load_rope();
 
     // ---- DMA bookkeeping (LW == 0 only): piece p of this wave is chunk c = w + p * NL of a stage ----
     const uint4* src[LW == 0 ? P : 1];
@@ -396,7 +396,7 @@ __global__ __launch_bounds__(64 * (WM * WN + LW)) void gemm_tile_kernel(GemmArgs
 
     if (a.db & 8) return;   // ablation: no epilogue
     // ---- epilogue: this wave's NTV x MTV tiles ----
-    if constexpr (EPI == EPI_QKV) {
+    if constexpr (epi_qkv(EPI)) {
         if constexpr (ROPE_LATE) load_rope();
         QkvCol qc;
         qc.init((ntw0 < ntiles ? ntw0 : ntiles - 1) * 16 + (lane >> 4) * 4, a.d, a.hd);
@@ -420,7 +420,11 @@ __global__ __launch_bounds__(64 * (WM * WN + LW)) void gemm_tile_kernel(GemmArgs
                             D::st4(a.out, ((size_t)m * a.H + qc.head) * a.hdp + qc.dd, x0, x1, x2, x3);
                         } else {
                             void* cache = qc.sec == 1 ? a.kc : a.vc;
-                            D::st4(cache, (((size_t)m * a.H + qc.head) * a.S8 + pos) * a.kvs + qc.dd, x0, x1, x2, x3);
+                            if constexpr (EPI == EPI_QKV8)   // fp8 slab: four e4m3 codes of the bf16-rounded values, byte offsets
+                                *(uint32_t*)((unsigned char*)cache + (((size_t)m * a.H + qc.head) * a.S8 + pos) * a.kvs + qc.dd) =
+                                    kv8_quant4(D::rnd(x0), D::rnd(x1), D::rnd(x2), D::rnd(x3), qc.sec == 1 ? a.k_inv : a.v_inv);
+                            else
+                                D::st4(cache, (((size_t)m * a.H + qc.head) * a.S8 + pos) * a.kvs + qc.dd, x0, x1, x2, x3);
                         }
                     }
                 }
@@ -532,7 +536,7 @@ template <typename D, int EPI, bool NORM>
 static int gt_dispatch(const GemmArgs& a, int wm, int wn, int mtv, int ntv, int kb, int stages, int lw, hipStream_t st) {
 #define GT_CASE(WM_, WN_, MTV_, NTV_, KB_, ST_, LW_)                                                                 \
     if (wm == WM_ && wn == WN_ && mtv == MTV_ && ntv == NTV_ && kb == KB_ && stages == ST_ && lw == LW_) {            \
-        if constexpr ((EPI == EPI_SWIGLU && (NTV_ % 2)) || (EPI == EPI_QKV && WM_ * WN_ == 8 && NTV_ == 8)) /* (spills at 168 VGPRs) */ \
+        if constexpr ((EPI == EPI_SWIGLU && (NTV_ % 2)) || (epi_qkv(EPI) && WM_ * WN_ == 8 && NTV_ == 8)) /* (spills at 168 VGPRs) */ \
             return LGEN_ERR_UNSUPPORTED;                                                                              \
         else return gt_launch<D, WM_, WN_, MTV_, NTV_, KB_, ST_, EPI, NORM, LW_>(a, st);                               \
     }
@@ -586,11 +590,12 @@ extern "C" int lgen_gemm_tile(const void* wp, const void* xp, void* out, int M, 
     return gt_dispatch_epi(a, epilogue_kind, wm, wn, mtv, ntv, kb, stages, lw, (hipStream_t)stream);
 }
 
-extern "C" int lgen_gemm_qkv_rope_tile(const void* wp, const void* xp, void* q_out, void* k_cache, void* v_cache, const float* freqs,
-                                       const int* pos_ptr, int M, int MTs, int d, int n_head, int hd, int hdp, int S8,
-                                       int kv_row_stride, int dtype, int wm, int wn, int mtv, int ntv, int kb, int stages, int lw,
-                                       const void* norm_w, const float* ssq_in, int ssq_parts, float eps, void* stream) {
-    if (dtype != LGEN_BF16) return LGEN_ERR_UNSUPPORTED;
+static int qkv_rope_tile_impl(const void* wp, const void* xp, void* q_out, void* k_cache, void* v_cache, const float* freqs,
+                              const int* pos_ptr, int M, int MTs, int d, int n_head, int hd, int hdp, int S8,
+                              int kv_row_stride, int dtype, int wm, int wn, int mtv, int ntv, int kb, int stages, int lw,
+                              const void* norm_w, const float* ssq_in, int ssq_parts, float eps, void* stream, bool kv8, float k_inv,
+                              float v_inv) {
+    if (dtype != LGEN_BF16 || (kv8 && hdp != 64)) return LGEN_ERR_UNSUPPORTED;
     if (d % 32 || (3 * d) % 16 || hd % 4 || hd < 16 || d != n_head * hd || M > MTs * 16 || M < 1) return LGEN_ERR_BAD_ARG;
     if (norm_w && (ssq_parts < 1 || ssq_parts > LGEN_SSQ_STRIDE)) return LGEN_ERR_BAD_ARG;
     GemmArgs a{};
@@ -603,6 +608,26 @@ extern "C" int lgen_gemm_qkv_rope_tile(const void* wp, const void* xp, void* q_o
     a.nw = (const uint4*)norm_w; a.ssq_in = ssq_in; a.parts = ssq_parts; a.eps = eps; a.inv_k = 1.0f / (float)d;
     a.passes = 1;
     a.db = gt_ablate();
+    a.k_inv = k_inv; a.v_inv = v_inv;
     if (!norm_w) return LGEN_ERR_UNSUPPORTED;
+    if (kv8) return gt_dispatch<BF16, EPI_QKV8, true>(a, wm, wn, mtv, ntv, kb, stages, lw, (hipStream_t)stream);
     return gt_dispatch<BF16, EPI_QKV, true>(a, wm, wn, mtv, ntv, kb, stages, lw, (hipStream_t)stream);
+}
+
+extern "C" int lgen_gemm_qkv_rope_tile(const void* wp, const void* xp, void* q_out, void* k_cache, void* v_cache, const float* freqs,
+                                       const int* pos_ptr, int M, int MTs, int d, int n_head, int hd, int hdp, int S8,
+                                       int kv_row_stride, int dtype, int wm, int wn, int mtv, int ntv, int kb, int stages, int lw,
+                                       const void* norm_w, const float* ssq_in, int ssq_parts, float eps, void* stream) {
+    return qkv_rope_tile_impl(wp, xp, q_out, k_cache, v_cache, freqs, pos_ptr, M, MTs, d, n_head, hd, hdp, S8, kv_row_stride, dtype, wm,
+                              wn, mtv, ntv, kb, stages, lw, norm_w, ssq_in, ssq_parts, eps, stream, false, 1.f, 1.f);
+}
+
+// The same launch with K / V appended to fp8 (e4m3) byte slabs (kv_row_stride in bytes): the EPI_QKV8 instantiations.
+extern "C" int lgen_gemm_qkv_rope_tile_kv8(const void* wp, const void* xp, void* q_out, void* k_cache, void* v_cache,
+                                           const float* freqs, const int* pos_ptr, int M, int MTs, int d, int n_head, int hd, int hdp,
+                                           int S8, int kv_row_stride, int dtype, int wm, int wn, int mtv, int ntv, int kb, int stages,
+                                           int lw, const void* norm_w, const float* ssq_in, int ssq_parts, float eps,
+                                           float k_inv_scale, float v_inv_scale, void* stream) {
+    return qkv_rope_tile_impl(wp, xp, q_out, k_cache, v_cache, freqs, pos_ptr, M, MTs, d, n_head, hd, hdp, S8, kv_row_stride, dtype, wm,
+                              wn, mtv, ntv, kb, stages, lw, norm_w, ssq_in, ssq_parts, eps, stream, true, k_inv_scale, v_inv_scale);
 }

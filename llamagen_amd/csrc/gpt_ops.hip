@@ -4,6 +4,7 @@
 //   lgen_rmsnorm      RMSNorm on the packed layout (gpt.py:137-148), two bf16 rounding points
 //   lgen_attn_decode  KV-cached single-query attention over kv_len = pos+1 keys only
 //                     (gpt.py:229-236 repeat_interleave + math-SDPA with causal_mask[:, pos])
+#include <type_traits>
 #include <utility>
 
 #include "gemm_epilogue.h"
@@ -223,12 +224,15 @@ struct AttnArgs {
     void* out;           // packed [d/KC][MTs][64][EPL]
     const int* pos_ptr;
     int pos_stride;      // 0: every row at *pos_ptr; 1: row b at pos_ptr[b] (continuous batching)
+    float kv8_vs;        // fp8 KV cache (lgen_attn_decode_kv8): s_v, applied to the normalised output.  (In the struct's former
+                         // padding word: sizeof(AttnArgs) and the argument layout of the existing kernels are unchanged.)
     const unsigned char* mask;  // null (pure causal) or causal_mask [B2][S8][S8] bytes: row `pos` is read
     int H, hd, hdp, S8, MTs;
-    float sf;            // sqrt(1/sqrt(hd))
+    float sf;            // sqrt(1/sqrt(hd)); fp8 KV cache: the one scale per score, sf^2 * s_k (kvs is then in BYTES)
     int kvs;             // elements between consecutive cache rows (hdp, or 2*hdp for an interleaved K|V slab)
     int mask_len;        // only keys < mask_len consult the mask row (t2i: the caption prefix); the rest is pure causal
 };
+static_assert(sizeof(AttnArgs) == 88, "AttnArgs grew: the argument layout (and ISA) of every attention kernel changes with it");
 
 // One group = CH wave-loads of K and of V = CH * KPL keys; both decode kernels below walk the keys of a (b, h) in such groups.
 // attn_load_group issues the loads of group g.  Row clamp smax: until the position is known the last slot of the slab (the first
@@ -236,8 +240,9 @@ struct AttnArgs {
 // last group re-read one line instead of fetching up to CH * KPL - 1 rows nobody looks at (round 5: on average 15.5 of 288.5 keys per
 // launch, 5 % of the kernel's HBM bytes -- the live PMC ratio 1.07 at positions 64 / 288 / 575 was exactly this).  live = false
 // (persistent kernel, look-ahead past its last item): kp / vp are the caller's dummy pointer and every load reads it at offset 0.
-template <int CH, int KPL>
-LGEN_DEV void attn_load_group(uint4 (&KB)[CH], uint4 (&VB)[CH], const uint4* kp, const uint4* vp, int g, int kin, int smax, int rpr,
+// VEC: what one lane loads of a key row -- uint4 (8 bf16 / fp16 or 4 fp32 elements), uint2 with an fp8 cache (8 e4m3 elements).
+template <int CH, int KPL, typename VEC>
+LGEN_DEV void attn_load_group(VEC (&KB)[CH], VEC (&VB)[CH], const VEC* kp, const VEC* vp, int g, int kin, int smax, int rpr,
                               bool live) {
 #pragma unroll
     for (int j = 0; j < CH; ++j) {
@@ -256,18 +261,29 @@ LGEN_DEV void attn_load_group(uint4 (&KB)[CH], uint4 (&VB)[CH], const uint4* kp,
 //                 per 8 elements instead of 8 unpacks + 8 multiplies + 8 fmas), scaled once by qk_scale = sf^2; qraw = q as loaded.
 //                 The products of two 8- / 11-bit mantissas are exact in fp32, so this differs from the first form by fp32
 //                 round-off only, like any other summation order (and v_dot2 flushes fp32 accumulator denormals).
-template <typename D, int LPK, int CH, bool DOT8>
-LGEN_DEV void attn_fold_group(const uint4 (&KB)[CH], const uint4 (&VB)[CH], int g, int kin, int kvlen, const unsigned char* pm,
+//   fp8 cache     (VEC = uint2, bf16 q): K and V unpack to fp32 exactly (4 x v_cvt_pk_f32_fp8 per 8 elements), q . k is an fmaf chain
+//                 on the RAW operands (qf = q unpacked, a bf16 x e4m3 product is exact in fp32) scaled once by qk_scale =
+//                 sf^2 * s_k; s_v is applied by the caller to the normalised output, so no scale sits in the loop.
+template <typename D, int LPK, int CH, bool DOT8, typename VEC>
+LGEN_DEV void attn_fold_group(const VEC (&KB)[CH], const VEC (&VB)[CH], int g, int kin, int kvlen, const unsigned char* pm,
                               int mask_len, const float (&qf)[D::EPL], const uint4& qraw, float qk_scale, float& m_run, float& l_run,
                               float (&acc)[D::EPL]) {
     constexpr int KPL = 64 / LPK, EPL = D::EPL;
+    constexpr bool KV8 = sizeof(VEC) == 8;
+    static_assert(!KV8 || (EPL == 8 && !DOT8), "fp8 cache: bf16 q, 8 elements per lane");
     float s[CH];
     float tmax = -1e30f;
 #pragma unroll
     for (int j = 0; j < CH; ++j) {
         const int key = g * (CH * KPL) + j * KPL + kin;
         float dot = 0.f;
-        if constexpr (DOT8) {
+        if constexpr (KV8) {
+            float kf[EPL];
+            kv8_unpack(KB[j], kf);
+#pragma unroll
+            for (int e = 0; e < EPL; ++e) dot = fmaf(qf[e], kf[e], dot);
+            dot *= qk_scale;
+        } else if constexpr (DOT8) {
             dot = D::dot8(KB[j], qraw) * qk_scale;
         } else {
             float kf[EPL];
@@ -292,7 +308,8 @@ LGEN_DEV void attn_fold_group(const uint4 (&KB)[CH], const uint4 (&VB)[CH], int 
         const float p = s[j] > -1e29f ? D::fexp(s[j] - m_new) : 0.f;
         l_run += p;
         float vf[EPL];
-        D::unpack(VB[j], vf);
+        if constexpr (KV8) kv8_unpack(VB[j], vf);
+        else D::unpack(VB[j], vf);
 #pragma unroll
         for (int e = 0; e < EPL; ++e) acc[e] = fmaf(p, vf[e], acc[e]);
     }
@@ -302,8 +319,11 @@ LGEN_DEV void attn_fold_group(const uint4 (&KB)[CH], const uint4 (&VB)[CH], int 
 // HPW (round 3): (batch row, head) pairs per workgroup.  At 256 chain rows the grid is 4096 (b, h) pairs; dispatching that many
 // 128-thread workgroups is 9 us of a 52 us average launch (kv_len 1: 9.0 us at 256 rows against 4.6 us at 64), so wide chains put
 // 2 or 4 heads of one row into a workgroup (same kv_len: the waves stay balanced across the one barrier).
-template <typename D, int LPK, int ATT_CH, int ATT_NW, int HPW>
-__global__ __launch_bounds__(64 * ATT_NW * HPW, (ATT_CH <= 2 ? 4 : 2)) void attn_decode_kernel(AttnArgs a) {
+// KV8: the caches are fp8 (e4m3) byte slabs -- a lane loads 8 bytes = 8 elements of a key row (the lanes per key stay hdp / 8 and the
+// cross-lane helpers unchanged), ATT_CH is twice the bf16 variant's so that the bytes in flight per wave are the same.
+template <typename D, int LPK, int ATT_CH, int ATT_NW, int HPW, bool KV8 = false>
+__global__ __launch_bounds__(64 * ATT_NW * HPW, (ATT_CH <= (KV8 ? 4 : 2) ? 4 : 2)) void attn_decode_kernel(AttnArgs a) {
+    typedef std::conditional_t<KV8, uint2, uint4> kv_t;
     constexpr int KPL = 64 / LPK;            // keys per wave-load
     constexpr int EPL = D::EPL;
     constexpr int GK = ATT_CH * KPL;         // keys per group
@@ -317,13 +337,13 @@ __global__ __launch_bounds__(64 * ATT_NW * HPW, (ATT_CH <= 2 ? 4 : 2)) void attn
     const int part = lane % LPK, kin = lane / LPK;
     const size_t rowbase = ((size_t)b * a.H + h) * a.S8;
     const int lpr = a.hdp / EPL;             // 16-byte pieces per key row (== LPK)
-    const int rpr = a.kvs / EPL;             // 16-byte pieces between consecutive rows of one cache
-    const uint4* kp = (const uint4*)a.kc + rowbase * rpr + part;
-    const uint4* vp = (const uint4*)a.vc + rowbase * rpr + part;
+    const int rpr = a.kvs / EPL;             // 16-byte pieces (fp8: 8-byte pieces, kvs in bytes) between consecutive rows of one cache
+    const kv_t* kp = (const kv_t*)a.kc + rowbase * rpr + part;
+    const kv_t* vp = (const kv_t*)a.vc + rowbase * rpr + part;
     int smax = a.S8 - 1;                     // row clamp of the key loads (attn_load_group)
 
-    uint4 k0[ATT_CH], v0[ATT_CH], k1[ATT_CH], v1[ATT_CH];
-    auto load = [&](uint4 (&KB)[ATT_CH], uint4 (&VB)[ATT_CH], int g) { attn_load_group<ATT_CH, KPL>(KB, VB, kp, vp, g, kin, smax, rpr, true); };
+    kv_t k0[ATT_CH], v0[ATT_CH], k1[ATT_CH], v1[ATT_CH];
+    auto load = [&](kv_t (&KB)[ATT_CH], kv_t (&VB)[ATT_CH], int g) { attn_load_group<ATT_CH, KPL>(KB, VB, kp, vp, g, kin, smax, rpr, true); };
     // group g of this wave: g = wv, wv + NW, ...; first group requested before pos is known
     int g = wv;
     const uint4 qv = ((const uint4*)a.q)[((size_t)b * a.H + h) * lpr + part];
@@ -334,14 +354,16 @@ __global__ __launch_bounds__(64 * ATT_NW * HPW, (ATT_CH <= 2 ? 4 : 2)) void attn
     smax = pos < smax ? pos : smax;
     float qf[EPL];
     D::unpack(qv, qf);
+    if constexpr (!KV8) {
 #pragma unroll
-    for (int e = 0; e < EPL; ++e) qf[e] *= a.sf;
+        for (int e = 0; e < EPL; ++e) qf[e] *= a.sf;
+    }
     const unsigned char* pm = a.mask ? a.mask + ((size_t)b * a.S8 + pos) * a.S8 : nullptr;
 
     float m_run = -1e30f, l_run = 0.f, acc[EPL];
 #pragma unroll
     for (int e = 0; e < EPL; ++e) acc[e] = 0.f;
-    auto fold = [&](const uint4 (&KB)[ATT_CH], const uint4 (&VB)[ATT_CH], int g) {   // every storage type: the fmaf form of q . k
+    auto fold = [&](const kv_t (&KB)[ATT_CH], const kv_t (&VB)[ATT_CH], int g) {   // every storage type: the fmaf form of q . k
         attn_fold_group<D, LPK, ATT_CH, false>(KB, VB, g, kin, kvlen, pm, a.mask_len, qf, qv, a.sf, m_run, l_run, acc);
     };
     while (g < ngroups) {
@@ -378,6 +400,7 @@ __global__ __launch_bounds__(64 * ATT_NW * HPW, (ATT_CH <= 2 ? 4 : 2)) void attn
             o += s_acc[hg][i][t] * f;
         }
         o = o / L;
+        if constexpr (KV8) o *= a.kv8_vs;
         D::st(a.out, D::xp_off(h * a.hd + t, b >> 4, b & 15, a.MTs), o);
     }
 }
@@ -431,8 +454,9 @@ extern "C" int lgen_ssq_group4(const float* ssq_in, float* ssq_out, int rows, in
 //     (three 256-row chains: 105 img/s against 85 with one).  Eight resident waves per CU at <= 128 VGPRs leave 256 registers per
 //     SIMD and all of the LDS to whatever else is in flight.
 // No LDS, no barriers; one (pos, kv_len) for all rows (generate()); per-row positions keep attn_decode_kernel.
-template <typename D, int LPK, int CH, int NWV>
+template <typename D, int LPK, int CH, int NWV, bool KV8 = false>
 __global__ __launch_bounds__(64 * NWV) void attn_decode_persist_kernel(AttnArgs a, int items, int total_waves) {
+    typedef std::conditional_t<KV8, uint2, uint4> kv_t;   // fp8 cache: as in attn_decode_kernel
     constexpr int KPL = 64 / LPK;            // keys per wave-load
     constexpr int EPL = D::EPL;
     constexpr int GK = CH * KPL;             // keys per group
@@ -441,15 +465,15 @@ __global__ __launch_bounds__(64 * NWV) void attn_decode_persist_kernel(AttnArgs 
     if (gw >= items) return;
     const int part = lane % LPK, kin = lane / LPK;
     const int lpr = a.hdp / EPL;             // 16-byte pieces per key row (== LPK)
-    const int rpr = a.kvs / EPL;             // 16-byte pieces between consecutive rows of one cache
+    const int rpr = a.kvs / EPL;             // 16-byte pieces (fp8: 8-byte pieces) between consecutive rows of one cache
     int smax = a.S8 - 1;                     // row clamp of the key loads (attn_load_group)
-    const uint4* const dummy = (const uint4*)a.q + part;   // where the look-ahead loads past the last item point (finite, L2-hot)
+    const kv_t* const dummy = (const kv_t*)a.q + part;   // where the look-ahead loads past the last item point (never folded, L2-hot)
 
-    uint4 k0[CH], v0[CH], k1[CH], v1[CH];
-    auto load = [&](uint4 (&KB)[CH], uint4 (&VB)[CH], int item, int g) {
+    kv_t k0[CH], v0[CH], k1[CH], v1[CH];
+    auto load = [&](kv_t (&KB)[CH], kv_t (&VB)[CH], int item, int g) {
         const bool live = item < items;      // wave-uniform; loads stay unconditional so that the waits stay counted
-        const uint4* kp = live ? (const uint4*)a.kc + (size_t)item * a.S8 * rpr + part : dummy;
-        const uint4* vp = live ? (const uint4*)a.vc + (size_t)item * a.S8 * rpr + part : dummy;
+        const kv_t* kp = live ? (const kv_t*)a.kc + (size_t)item * a.S8 * rpr + part : dummy;
+        const kv_t* vp = live ? (const kv_t*)a.vc + (size_t)item * a.S8 * rpr + part : dummy;
         attn_load_group<CH, KPL>(KB, VB, kp, vp, g, kin, smax, rpr, live);
     };
     // the first group and q of the first item are requested before the position is known
@@ -468,10 +492,12 @@ __global__ __launch_bounds__(64 * NWV) void attn_decode_persist_kernel(AttnArgs 
     int ci = gw, cg = 0;                      // compute cursor
     float qf[EPL], m_run = -1e30f, l_run = 0.f, acc[EPL];
     uint4 qn = qv, qraw = qv;
-    constexpr bool DOT8 = D::ESZ == 2;       // 16-bit storage (round 6): the packed-dot form of q . k, see attn_fold_group
-    const float qk_scale = DOT8 ? a.sf * a.sf : a.sf;
+    constexpr bool DOT8 = D::ESZ == 2 && !KV8;   // 16-bit storage (round 6): the packed-dot form of q . k, see attn_fold_group
+    const float qk_scale = DOT8 ? a.sf * a.sf : a.sf;   // (fp8 cache: a.sf is sf^2 * s_k already)
     auto begin_item = [&]() {
-        if constexpr (DOT8) {
+        if constexpr (KV8) {
+            D::unpack(qn, qf);               // raw q: the scale sf^2 * s_k is applied once per key
+        } else if constexpr (DOT8) {
             qraw = qn;
         } else {
             D::unpack(qn, qf);
@@ -485,7 +511,7 @@ __global__ __launch_bounds__(64 * NWV) void attn_decode_persist_kernel(AttnArgs 
         qn = ((const uint4*)a.q)[(size_t)(nxt < items ? nxt : ci) * lpr + part];
     };
     begin_item();
-    auto fold = [&](const uint4 (&KB)[CH], const uint4 (&VB)[CH]) {
+    auto fold = [&](const kv_t (&KB)[CH], const kv_t (&VB)[CH]) {
         const unsigned char* pm = a.mask ? a.mask + ((size_t)(ci / a.H) * a.S8 + pos) * a.S8 : nullptr;
         attn_fold_group<D, LPK, CH, DOT8>(KB, VB, cg, kin, kvlen, pm, a.mask_len, qf, qraw, qk_scale, m_run, l_run, acc);
     };
@@ -501,7 +527,11 @@ __global__ __launch_bounds__(64 * NWV) void attn_decode_persist_kernel(AttnArgs 
 #pragma unroll
             for (int e = 0; e < EPL; ++e) {
                 const int t = lane * EPL + e;
-                if (t < a.hd) D::st(a.out, D::xp_off(h * a.hd + t, b >> 4, b & 15, a.MTs), acc[e] / l_run);
+                if constexpr (KV8) {
+                    if (t < a.hd) D::st(a.out, D::xp_off(h * a.hd + t, b >> 4, b & 15, a.MTs), acc[e] / l_run * a.kv8_vs);
+                } else {
+                    if (t < a.hd) D::st(a.out, D::xp_off(h * a.hd + t, b >> 4, b & 15, a.MTs), acc[e] / l_run);
+                }
             }
         }
         cg = 0;
@@ -560,16 +590,17 @@ constexpr AttnVariant ATTN_VARIANTS[] = {
 constexpr int ATTN_NVARIANTS = sizeof(ATTN_VARIANTS) / sizeof(ATTN_VARIANTS[0]);
 
 // launch geometry and kernel instantiation of table entry V (two entries with equal template arguments share one kernel)
-template <typename D, int LPK, int V>
+template <typename D, int LPK, int V, bool KV8 = false>
 static void launch_attn_variant(const AttnArgs& a, int B2, hipStream_t st) {
     constexpr AttnVariant v = ATTN_VARIANTS[V];
+    constexpr int CH = KV8 ? 2 * v.ch : v.ch;   // fp8 cache: 8-byte loads, twice as many per group (the same bytes in flight)
     if constexpr (v.persistent) {
         const int items = B2 * a.H;
         int wgs = lgen_cu_count() * v.wg_per_cu;
         if (wgs * v.nw > items) wgs = (items + v.nw - 1) / v.nw;
-        hipLaunchKernelGGL((attn_decode_persist_kernel<D, LPK, v.ch, v.nw>), dim3(wgs), dim3(64 * v.nw), 0, st, a, items, wgs * v.nw);
+        hipLaunchKernelGGL((attn_decode_persist_kernel<D, LPK, CH, v.nw, KV8>), dim3(wgs), dim3(64 * v.nw), 0, st, a, items, wgs * v.nw);
     } else {
-        hipLaunchKernelGGL((attn_decode_kernel<D, LPK, v.ch, v.nw, v.hpw>), dim3(B2 * a.H / v.hpw), dim3(64 * v.nw * v.hpw), 0, st, a);
+        hipLaunchKernelGGL((attn_decode_kernel<D, LPK, CH, v.nw, v.hpw, KV8>), dim3(B2 * a.H / v.hpw), dim3(64 * v.nw * v.hpw), 0, st, a);
     }
 }
 template <typename D, int LPK, int... V>
@@ -580,7 +611,7 @@ static void launch_attn_decode(int variant, std::integer_sequence<int, V...>, co
 static int attn_decode_impl(const void* q, const void* k_cache, const void* v_cache, void* out_packed,
                             const int* pos_ptr, int pos_stride, const unsigned char* mask, int mask_len, int B2, int MTs,
                             int n_head, int hd, int hdp, int S8, int kv_row_stride, int dtype, int variant, void* stream) {
-    AttnArgs a{q, k_cache, v_cache, out_packed, pos_ptr, pos_stride, mask, n_head, hd, hdp, S8, MTs, 0.f,
+    AttnArgs a{q, k_cache, v_cache, out_packed, pos_ptr, pos_stride, 0.f, mask, n_head, hd, hdp, S8, MTs, 0.f,
                kv_row_stride > 0 ? kv_row_stride : hdp, mask_len > 0 ? mask_len : S8};
     if (variant < -1 || variant >= ATTN_NVARIANTS) return LGEN_ERR_BAD_ARG;
     a.sf = sqrtf(1.0f / sqrtf((float)hd));
@@ -616,6 +647,26 @@ extern "C" int lgen_attn_decode_rows(const void* q, const void* k_cache, const v
                                      int n_head, int hd, int hdp, int S8, int kv_row_stride, int dtype, int variant, void* stream) {
     return attn_decode_impl(q, k_cache, v_cache, out_packed, row_pos, 1, mask, mask_len, B2, MTs, n_head, hd, hdp, S8,
                             kv_row_stride, dtype, variant, stream);
+}
+
+// lgen_attn_decode on fp8 (e4m3) K/V byte slabs (lgen.h "FP8 KV cache"): bf16 q and output, hdp = 64, one position for all rows.
+// The workgroup form (variant 2) below 256 rows, the persistent form (variant 10) from 256 rows; 8 lanes per key, 8 bytes per lane.
+extern "C" int lgen_attn_decode_kv8(const void* q, const void* k_cache, const void* v_cache, void* out_packed, const int* pos_ptr,
+                                    const unsigned char* mask, int mask_len, int B2, int MTs, int n_head, int hd, int hdp, int S8,
+                                    int kv_row_stride, int dtype, int variant, float k_scale, float v_scale, void* stream) {
+    if (dtype != LGEN_BF16 || hdp != 64) return LGEN_ERR_UNSUPPORTED;
+    if (variant < 0) variant = B2 >= 256 ? 10 : 2;
+    if (variant != 2 && variant != 10) return LGEN_ERR_UNSUPPORTED;
+    AttnArgs a{q, k_cache, v_cache, out_packed, pos_ptr, 0, v_scale, mask, n_head, hd, hdp, S8, MTs, 0.f,
+               kv_row_stride > 0 ? kv_row_stride : hdp, mask_len > 0 ? mask_len : S8};
+    // the stride is in bytes; a lane's piece is 8 bytes, and a row holds at least hd rounded up to one piece
+    if (hd > hdp || hd < 1 || B2 < 1 || B2 > MTs * 16 || S8 < 1 || a.kvs < (hd + 7) / 8 * 8 || a.kvs % 8) return LGEN_ERR_BAD_ARG;
+    const float sf = sqrtf(1.0f / sqrtf((float)hd));
+    a.sf = sf * sf * k_scale;
+    if (variant == 10) launch_attn_variant<BF16, 8, 10, true>(a, B2, (hipStream_t)stream);
+    else launch_attn_variant<BF16, 8, 2, true>(a, B2, (hipStream_t)stream);
+    LGEN_CHECK_LAUNCH();
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------

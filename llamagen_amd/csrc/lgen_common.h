@@ -245,6 +245,30 @@ LGEN_DEV uint4 ldg_nt(const uint4* p) {  // streamed-once data (weights): non-te
     return make_uint4(v[0], v[1], v[2], v[3]);
 }
 
+typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
+LGEN_DEV uint2 ldg_nt(const uint2* p) {  // 8-byte form: one fp8 KV-cache piece (8 elements) per lane
+    u32x2_t v = __builtin_nontemporal_load((const u32x2_t*)p);
+    return make_uint2(v[0], v[1]);
+}
+
+// ---- fp8 KV cache (lgen.h "FP8 KV cache"): OCP e4m3fn, gfx950's native fp8 ----
+// Four cache elements from four values x the bf16 path would have stored: q = rne_e4m3(clamp(x * inv_s, -448, 448)), one fp32
+// multiply (-ffp-contract=off), the clamp explicit so that the stored code never depends on the conversion's overflow mode (a NaN
+// stays NaN: the comparisons are false).  Two v_cvt_pk_fp8_f32 into one dword, element 0 in the low byte.
+LGEN_DEV float kv8_clamp(float x) { return x < -448.f ? -448.f : (x > 448.f ? 448.f : x); }
+LGEN_DEV uint32_t kv8_quant4(float x0, float x1, float x2, float x3, float inv_s) {
+    int w = 0;
+    w = __builtin_amdgcn_cvt_pk_fp8_f32(kv8_clamp(x0 * inv_s), kv8_clamp(x1 * inv_s), w, false);
+    w = __builtin_amdgcn_cvt_pk_fp8_f32(kv8_clamp(x2 * inv_s), kv8_clamp(x3 * inv_s), w, true);
+    return (uint32_t)w;
+}
+// the 8 elements of one lane's 8 bytes as fp32 (exact): 4 x v_cvt_pk_f32_fp8
+LGEN_DEV void kv8_unpack(const uint2& u, float (&f)[8]) {
+    const f32x2_t a = __builtin_amdgcn_cvt_pk_f32_fp8((int)u.x, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)u.x, true);
+    const f32x2_t c = __builtin_amdgcn_cvt_pk_f32_fp8((int)u.y, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)u.y, true);
+    f[0] = a[0]; f[1] = a[1]; f[2] = b[0]; f[3] = b[1]; f[4] = c[0]; f[5] = c[1]; f[6] = d[0]; f[7] = d[1];
+}
+
 LGEN_DEV float4 ldg_nt_f4(const float4* p) {  // streamed-once fp32 data
     f32x4_t v = __builtin_nontemporal_load((const f32x4_t*)p);
     return make_float4(v[0], v[1], v[2], v[3]);

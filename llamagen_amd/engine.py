@@ -96,10 +96,25 @@ _PACKED = weakref.WeakKeyDictionary()  # tok_embeddings module (shared by lane v
 
 
 class DecodeEngine:
-    def __init__(self, model, max_batch: int, S8: int, dtype: torch.dtype):
+    def __init__(self, model, max_batch: int, S8: int, dtype: torch.dtype, kv_dtype: Optional[str] = None, kv_scales=None):
+        """kv_dtype None: K/V in the storage dtype.  "fp8_e4m3" (opt-in, Transformer.set_kv_cache): uint8 slabs of OCP e4m3fn codes,
+        kv_scales = (k_scales, v_scales), one float per layer (default 1.0); bf16 storage and head_dim <= 64 only."""
         cfg = model.config
         if dtype not in (torch.bfloat16, torch.float32, torch.float16):
             raise NotImplementedError(f"the HIP engine implements --precision bf16, fp16 and none (fp32), not {dtype}")
+        if kv_dtype is not None:
+            if kv_dtype != "fp8_e4m3":
+                raise ValueError(f"kv_dtype {kv_dtype!r}: expected None or 'fp8_e4m3'")
+            if dtype != torch.bfloat16:
+                raise NotImplementedError(f"fp8 KV cache: bf16 storage only, not {dtype} (the append and attention kernels read bf16 q)")
+            if cfg.dim // cfg.n_head > 64:
+                raise NotImplementedError(f"fp8 KV cache: head_dim {cfg.dim // cfg.n_head} > 64 has no kernels (64-byte key rows only)")
+        self.kv_dtype = kv_dtype
+        ks, vs = kv_scales if kv_scales is not None else (None, None)
+        self.k_scales = tuple(float(x) for x in ks) if ks is not None else (1.0,) * cfg.n_layer
+        self.v_scales = tuple(float(x) for x in vs) if vs is not None else (1.0,) * cfg.n_layer
+        if len(self.k_scales) != cfg.n_layer or len(self.v_scales) != cfg.n_layer:
+            raise ValueError("kv_scales: one (k, v) scale per layer")
         self.lib = L.lib()
         # decode-attention kernel variant: -1 = the library's choice by shape (lgen.h); LGEN_ATTN_VARIANT=n pins one (development)
         self.attn_variant = int(os.environ.get("LGEN_ATTN_VARIANT", "-1"))
@@ -136,7 +151,15 @@ class DecodeEngine:
         # slabs by default; LGEN_KV_INTERLEAVE=1 puts the K and V row of a slot next to each other
         # ([.., S8, 2, hdp], row stride 2*hdp: one HBM stream per (b, h) instead of two) -- measured 1.4 % SLOWER
         # in the decode attention at kv_len 576 on MI355X, so it stays an option of the kernels' row-stride argument.
-        if os.environ.get("LGEN_KV_INTERLEAVE") == "1":
+        if kv_dtype is not None:
+            # fp8 slabs [L][B2][H][S8][kvs8] BYTES, kvs8 = hd rounded up to 16; zero-initialised (a zero byte is +0.0) and followed
+            # by 64 readable zero bytes: the attention reads 64 bytes per key whatever the stride (the slack rule of the bf16 slabs)
+            self.kvs = _ceil_div(self.hd, 16) * 16
+            n = self.L * max_batch * self.H * S8 * self.kvs
+            self._k_flat, self._v_flat = z(n + 64, dtype=torch.uint8), z(n + 64, dtype=torch.uint8)
+            self.k_cache = self._k_flat[:n].view(self.L, max_batch, self.H, S8, self.kvs)
+            self.v_cache = self._v_flat[:n].view(self.L, max_batch, self.H, S8, self.kvs)
+        elif os.environ.get("LGEN_KV_INTERLEAVE") == "1":
             self.kv_slab = z(self.L, max_batch, self.H, S8, 2, self.hdp)
             self.k_cache, self.v_cache = self.kv_slab[..., 0, :], self.kv_slab[..., 1, :]
             self.kvs = 2 * self.hdp
@@ -205,6 +228,8 @@ class DecodeEngine:
         rows would otherwise run the generic norm-prologue kernel, slower than stand-alone norm + the wide ring shapes.
         The fused / unfused choice is the `fuse_norm` property below -- nothing is flipped here (the flip used to stick
         after serving); only the captured graphs of the other mode are dropped, in BOTH directions."""
+        if value is not None and self.kv_dtype is not None:
+            raise NotImplementedError("per-row positions (continuous batching) have no fp8 KV cache form")
         before = self.fuse_norm if hasattr(self, "_fuse_auto") else None
         self._pos_rows = value
         if before is not None and self.fuse_norm != before:
@@ -247,8 +272,17 @@ class DecodeEngine:
         self._wsig = sig
         self._graphs = {}
 
-    def compatible(self, model, max_batch, S8, dtype) -> bool:
-        return (self.B2 == max_batch and self.S8 == S8 and self.dtype == dtype
+    def _kv_key(self):
+        """KV format and scales: launch constants of the append / attention kernels (part of compatible() and of the graph key)."""
+        return (self.kv_dtype, self.k_scales, self.v_scales) if self.kv_dtype is not None else (None,)
+
+    def compatible(self, model, max_batch, S8, dtype, kv_dtype=None, kv_scales=None) -> bool:
+        if kv_dtype is None:
+            want = (None,)
+        else:
+            ks, vs = kv_scales if kv_scales is not None else ((1.0,) * self.L, (1.0,) * self.L)
+            want = (kv_dtype, tuple(float(x) for x in ks), tuple(float(x) for x in vs))
+        return (self.B2 == max_batch and self.S8 == S8 and self.dtype == dtype and self._kv_key() == want
                 and self.dev == model.tok_embeddings.weight.device and self._wsig == self._sig(model))
 
     def reset(self, max_batch: int):
@@ -339,6 +373,23 @@ class DecodeEngine:
         rows = self.pos_rows is not None
         pos_ptr = self.pos_rows.data_ptr() if rows else self.state.data_ptr()
         g = self.plan["qkv"]
+        if self.kv_dtype is not None:   # fp8 slabs: the *_kv8 twins with layer i's inverse scales (fp32(1 / s), computed here)
+            inv = (1.0 / self.k_scales[i], 1.0 / self.v_scales[i])
+            if g.shape is not None and nw is not None:
+                sq, parts = self._tile_stats(g)
+                rc = lib.lgen_gemm_qkv_rope_tile_kv8(L.ptr(w["wqkv"]), L.ptr(x_in), L.ptr(self.qbuf), L.ptr(self.k_cache[i]),
+                                                     L.ptr(self.v_cache[i]), L.ptr(self.freqs_cis), pos_ptr, M, mts, d, H, hd, hdp, S8,
+                                                     self.kvs, dt, *g.shape, L.ptr(nw), L.ptr(sq), parts, self.eps, *inv, st)
+                if rc != L.ERR_UNSUPPORTED:
+                    L.check(rc, "gemm_qkv_rope_tile_kv8")
+                    return
+                g = self._refuse_tile("qkv")
+            L.check(lib.lgen_gemm_qkv_rope_kv8(L.ptr(w["wqkv"]), L.ptr(x_in), L.ptr(self.qbuf), L.ptr(self.k_cache[i]),
+                                               L.ptr(self.v_cache[i]), L.ptr(self.freqs_cis), pos_ptr, M, mts, d, H, hd, hdp, S8,
+                                               self.kvs, dt, *g.tiles, L.ptr(nw), L.ptr(self.ssq if nw is not None else None),
+                                               self.ssq_parts, self.eps, g.passes[0] if nw is not None else 1, *inv, st),
+                    "gemm_qkv_rope_kv8")
+            return
         if g.shape is not None and nw is not None:
             sq, parts = self._tile_stats(g)
             rc = lib.lgen_gemm_qkv_rope_tile(L.ptr(w["wqkv"]), L.ptr(x_in), L.ptr(self.qbuf), L.ptr(self.k_cache[i]),
@@ -400,9 +451,14 @@ class DecodeEngine:
             if self._prof is not None:  # bench.py roofline leg: HIP events on the launch stream
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
-            L.check(attn_fn(L.ptr(self.qbuf), L.ptr(self.k_cache[i]), L.ptr(self.v_cache[i]), L.ptr(self.ap),
-                            pos_ptr, L.ptr(pm), self.T if pm is not None else 0, M, mts, H, hd, hdp, S8, self.kvs, dt, self.attn_variant, st),
-                    "attn_decode")
+            if self.kv_dtype is not None:
+                L.check(lib.lgen_attn_decode_kv8(L.ptr(self.qbuf), L.ptr(self.k_cache[i]), L.ptr(self.v_cache[i]), L.ptr(self.ap),
+                                                 pos_ptr, L.ptr(pm), self.T if pm is not None else 0, M, mts, H, hd, hdp, S8, self.kvs,
+                                                 dt, self.attn_variant, self.k_scales[i], self.v_scales[i], st), "attn_decode_kv8")
+            else:
+                L.check(attn_fn(L.ptr(self.qbuf), L.ptr(self.k_cache[i]), L.ptr(self.v_cache[i]), L.ptr(self.ap),
+                                pos_ptr, L.ptr(pm), self.T if pm is not None else 0, M, mts, H, hd, hdp, S8, self.kvs, dt, self.attn_variant, st),
+                        "attn_decode")
             if self._prof is not None:
                 e1.record()
                 self._prof["events"].append((e0, e1))
@@ -479,6 +535,9 @@ class DecodeEngine:
         lib, st, dt = self.lib, L.stream(), self.dt
         B2, T, d = emb.shape
         F, H, hd, hdp, S8 = self.F, self.H, self.hd, self.hdp, self.S8
+        if self.kv_dtype is not None:
+            raise NotImplementedError("whole-sequence passes (score(), forward(idx, cond_idx), the batched t2i prefill) run the prefill "
+                                      "kernels, which have no fp8 KV cache form: unset it with model.set_kv_cache(None) (and LGEN_KV_DTYPE)")
         if B2 != self.B2 or T > S8:
             raise ValueError(f"sequence forward of [{B2}, {T}] rows on caches set up for [{self.B2}, {S8}]")
         R = B2 * T
@@ -654,7 +713,7 @@ class DecodeEngine:
             self._layers_and_logits()
         else:
             emb = self.caption_embed(cond_combined)
-            if os.environ.get("LGEN_SEQ_PREFILL") == "1" or T > 128:
+            if os.environ.get("LGEN_SEQ_PREFILL") == "1" or T > 128 or self.kv_dtype is not None:   # (fp8 KV cache: decode kernels only)
                 for t in range(T):  # causal prefix, one position at a time through the decode kernels
                     self.state[0] = t
                     self._set_residual(emb[:, t])
@@ -667,7 +726,7 @@ class DecodeEngine:
         self._sample(B, sp, logp)
         yield 0
         # ---- decode (generate.py:105-123): every step first advances (pos, step)
-        key = (B, N, self._mask() is not None, self.fuse_norm, self.use_tile, tuple(sorted(self.tile_shape_override.items())),
+        key = (B, N, self._kv_key(), self._mask() is not None, self.fuse_norm, self.use_tile, tuple(sorted(self.tile_shape_override.items())),
                tuple(sorted(self.tile_override.items())),
                tuple(sorted(self.pass_override.items())), sp["use_cfg"], sp["cfg_scale"],
                sp["cfg_interval"], sp["temperature"], sp["top_k"], sp["top_p"], sp["sample_logits"],

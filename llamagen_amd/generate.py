@@ -11,6 +11,8 @@ from __future__ import annotations
 
 import torch
 
+from .gpt import kv_cache_refuse
+
 
 @torch.no_grad()
 def generate(model, cond, max_new_tokens, emb_masks=None, cfg_scale=1.0, cfg_interval=-1, **sampling_kwargs):
@@ -128,6 +130,7 @@ def score(model, cond, ids, emb_masks=None, cfg_scale=1.0, temperature=1.0):
     kind = model.model_type
     if kind not in ("c2i", "t2i"):
         raise Exception("please check model type")
+    kv_cache_refuse(model, "score()")
     if ids.dim() != 2 or ids.shape[0] != cond.shape[0] or ids.shape[1] < 1:
         raise ValueError("ids must be [B, N] with one row per conditioning row")
     use_cfg = cfg_scale > 1.0

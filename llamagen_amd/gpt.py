@@ -14,6 +14,8 @@ raise NotImplementedError.
 """
 from __future__ import annotations
 
+import math
+import os
 from dataclasses import dataclass
 from typing import List, Optional
 
@@ -142,9 +144,72 @@ class _Block(nn.Module):
         self.ffn_norm = _Norm(cfg.dim, cfg.norm_eps)
 
 
+KV_CACHE_DTYPES = ("fp8_e4m3",)
+
+
+def _kv_scale_list(name, value, n_layer):
+    """A float or a per-layer sequence -> n_layer positive finite floats (None: unit scales)."""
+    if value is None:
+        return (1.0,) * n_layer
+    vals = [float(value)] * n_layer if isinstance(value, (int, float)) else [float(v) for v in value]
+    if len(vals) != n_layer:
+        raise ValueError(f"{name}: {len(vals)} values for {n_layer} layers (give one float or one value per layer)")
+    for v in vals:
+        if not (math.isfinite(v) and v > 0.0):
+            raise ValueError(f"{name}: scales must be positive and finite, got {v}")
+    return tuple(vals)
+
+
+def kv_cache_config(model):
+    """The KV-cache format selected for `model`: (None, None, None) = the storage dtype (default), else
+    ("fp8_e4m3", k_scales, v_scales) with one float per layer.  Set by Transformer.set_kv_cache(); with nothing set on the model the
+    environment variable LGEN_KV_DTYPE=fp8_e4m3 selects fp8 with unit scales (so that unmodified drivers can be run on it)."""
+    cfg = getattr(model, "_kv_cache", None)
+    if cfg is not None:
+        return cfg
+    env = os.environ.get("LGEN_KV_DTYPE", "")
+    if env in ("", "auto"):
+        return None, None, None
+    if env not in KV_CACHE_DTYPES:
+        raise ValueError(f"LGEN_KV_DTYPE={env!r}: expected one of {KV_CACHE_DTYPES} (or unset)")
+    n = int(getattr(model, "n_layer", 0)) or len(model.layers)
+    return env, (1.0,) * n, (1.0,) * n
+
+
+def kv_cache_refuse(model, what):
+    """Raise for an operation the fp8 KV cache does not cover (it runs the prefill kernels on the slabs)."""
+    if kv_cache_config(model)[0] is not None:
+        raise NotImplementedError(f"{what} is not implemented with an fp8 KV cache: unset it with model.set_kv_cache(None) "
+                                  "(and LGEN_KV_DTYPE) first")
+
+
+def kv_scales_from_caches(model, headroom: float = 2.0):
+    """Per-layer fp8 scales measured on the caches a bf16 (or fp16 / fp32) generate() just filled: ([s_k per layer], [s_v per
+    layer]) with s = headroom * amax / 448 rounded UP to a power of two, amax over the slots that run wrote (0 .. last position).
+    Host-side torch on the engine's slabs, for callers with real checkpoints: model.set_kv_cache("fp8_e4m3", *kv_scales_from_caches(
+    model)).  `headroom` is the caller's margin for values later prompts may reach; it is not a tuned constant."""
+    eng = getattr(model, "_engine", None)
+    if eng is None:
+        raise RuntimeError("kv_scales_from_caches: run generate() with the default KV cache first")
+    if eng.kv_dtype is not None:
+        raise RuntimeError("kv_scales_from_caches reads the storage-dtype caches: call it before set_kv_cache('fp8_e4m3')")
+    if not (math.isfinite(headroom) and headroom > 0):
+        raise ValueError(f"headroom must be positive, got {headroom}")
+    n = int(eng.state[0].item()) + 1
+    out = ([], [])
+    for i in range(eng.L):
+        for dst, slab in zip(out, (eng.k_cache[i], eng.v_cache[i])):
+            amax = float(slab[:, :, :n, : eng.hd].float().abs().max().item())
+            x = headroom * amax / 448.0
+            dst.append(2.0 ** math.ceil(math.log2(x)) if x > 0 and math.isfinite(x) else 1.0)
+    return out
+
+
 class KVCacheView:
     """What `layer.attention.kv_cache` exposes after setup_caches (gpt.py:170-185): views into
-    the engine's [L, B, H, S8, hd_pad] cache slabs."""
+    the engine's [L, B, H, S8, row] cache slabs.  With an fp8 KV cache selected (Transformer.set_kv_cache) these are the uint8
+    slabs: one OCP e4m3fn code per element, rows of head_dim rounded up to 16 bytes; value = code.view(torch.float8_e4m3fn) * scale
+    of that layer."""
 
     def __init__(self, k: torch.Tensor, v: torch.Tensor):
         self.k_cache = k
@@ -182,6 +247,34 @@ class Transformer(nn.Module):
         self.freqs_cis = None
         self._engine = None
         self._prof = None
+        # set_kv_cache(): [None] = storage dtype, else [("fp8_e4m3", k_scales, v_scales)].  A one-element list, so that the lane
+        # views of this model (shallow copies, lane_view()) share the SETTING, not a snapshot of it: set_kv_cache() on the model
+        # after a SamplingPipeline exists reaches every lane at its next setup_caches()
+        self._kv_shared = [None]
+
+    @property
+    def _kv_cache(self):
+        return self._kv_shared[0]
+
+    def set_kv_cache(self, dtype=None, k_scales=None, v_scales=None):
+        """KV-cache element format of the decode engine: None (default) keeps the storage dtype, "fp8_e4m3" stores K and V as OCP
+        e4m3fn bytes, q = rne(clamp(x / s, -448, 448)) with one (s_k, s_v) pair per layer -- `k_scales` / `v_scales` are a float or
+        a per-layer sequence, default 1.0 (see kv_scales_from_caches for scales measured on a checkpoint).  Half the KV bytes the
+        decode attention reads and half the KV memory.  Covers generate() / generate_iter() / SamplingPipeline with bf16 storage
+        and head_dim <= 64; score(), whole-sequence forward and the continuous batcher raise NotImplementedError while it is set.
+        Takes effect at the next setup_caches() (generate() calls it): the engine and its captured graph are rebuilt.  The
+        setting is shared with every lane_view() of this model, whether taken before or after this call."""
+        if dtype in (None, "auto"):
+            if k_scales is not None or v_scales is not None:
+                raise ValueError("k_scales / v_scales need dtype='fp8_e4m3'")
+            self._kv_shared[0] = None
+            return
+        if dtype not in KV_CACHE_DTYPES:
+            raise ValueError(f"kv cache dtype {dtype!r}: expected None or one of {KV_CACHE_DTYPES}")
+        hd = self.config.dim // self.config.n_head
+        if hd > 64:
+            raise NotImplementedError(f"fp8 KV cache: head_dim {hd} > 64 has no kernels (only the 64-byte key rows of GPT-B/L/XL/XXL)")
+        self._kv_shared[0] = (dtype, _kv_scale_list("k_scales", k_scales, self.n_layer), _kv_scale_list("v_scales", v_scales, self.n_layer))
 
     # ---- reference API -------------------------------------------------------------
     def setup_caches(self, max_batch_size: int, max_seq_length: int, dtype: torch.dtype):
@@ -195,8 +288,10 @@ class Transformer(nn.Module):
                 "llamagen_amd.Transformer runs only on an AMD GPU through the HIP library "
                 "(no CPU fallback); move the model to 'cuda' first")
         S8 = find_multiple(max_seq_length, 8)
-        if self._engine is None or not self._engine.compatible(self, max_batch_size, S8, dtype):
-            self._engine = DecodeEngine(self, max_batch_size, S8, dtype)
+        kv_dtype, k_scales, v_scales = kv_cache_config(self)
+        kv_scales = None if kv_dtype is None else (k_scales, v_scales)
+        if self._engine is None or not self._engine.compatible(self, max_batch_size, S8, dtype, kv_dtype, kv_scales):
+            self._engine = DecodeEngine(self, max_batch_size, S8, dtype, kv_dtype=kv_dtype, kv_scales=kv_scales)
         eng = self._engine
         eng.reset(max_batch_size)
         self.max_seq_length = S8
@@ -217,6 +312,7 @@ class Transformer(nn.Module):
         if mask is not None:
             raise NotImplementedError("explicit attention masks are not part of the reference's call sites for forward")
         if idx is not None and cond_idx is not None:
+            kv_cache_refuse(self, "the whole-sequence forward(idx, cond_idx)")
             B, S = idx.shape[0], self.cls_token_num + idx.shape[1]
             dtype = self.tok_embeddings.weight.dtype
             if self._engine is None or not self._engine.compatible(self, B, max(find_multiple(S, 8), self.max_seq_length), dtype):

@@ -55,7 +55,7 @@ import torch
 
 from . import _lib as L
 from .engine import DecodeEngine
-from .gpt import find_multiple
+from .gpt import find_multiple, kv_cache_refuse
 
 
 def bucket_ladder(slots: int, slot_buckets: Optional[Sequence[int]]) -> List[int]:
@@ -179,6 +179,7 @@ class ContinuousBatcher:
                  slot_buckets: Optional[Sequence[int]] = None, shrink_after: int = 8):
         if model.model_type not in ("c2i", "t2i"):
             raise Exception("please check model type")
+        kv_cache_refuse(model, "the continuous batcher (per-row positions)")
         dev = model.tok_embeddings.weight.device
         self.model, self.dev = model, dev
         self.num_classes, self.V = int(model.num_classes), int(model.config.vocab_size)
