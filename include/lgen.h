@@ -15,8 +15,8 @@
  * lgen_conv_wino (the Winograd experiment of round 5 left the product library: tools/experiments/conv_wino/); ABI v10 = v9 +
  * lgen_ssq_group4 (row statistics pre-grouped for the fused-norm consumers) and key-row stride checks in the prefill entry points;
  * v10 + lgen_sample_rows_params is additive (a new symbol, nothing else changes), so the version number stays 10; so are
- * lgen_sample_logprob, lgen_sample_rows_params_logprob and lgen_logprob_rows (per-token log-probabilities), and the three *_kv8
- * entry points of the opt-in FP8 KV cache.  Each entry point
+ * lgen_sample_logprob, lgen_sample_rows_params_logprob and lgen_logprob_rows (per-token log-probabilities), the three *_kv8
+ * entry points of the opt-in FP8 KV cache, and lgen_sample_given / lgen_sample_rows_params_given (image completion).  Each entry point
  * cites the reference op sequence it replaces (paths relative to the reference repository root).
  *
  * Fragment-packed layouts ("chunk" = 1 KiB = [16 rows][KC k] in MFMA operand order, lane =
@@ -221,6 +221,20 @@ int lgen_sample_logprob(const void* logits, const float* noise, long long noise_
                         const int* state, int B, int V, int seq_stride, int use_cfg, float cfg_scale, int cfg_interval,
                         float temperature, int top_k, float top_p, int greedy, int dtype, float* logprob_out, void* stream);
 
+/* Image completion ("these tokens are fixed, sample the rest"; the prompt tokens of the reference's serving fork,
+ * serve/llm.py:141-210): lgen_sample_logprob with GIVEN tokens.  given [B][seq_stride] int32, indexed like seq: the entry of
+ * (b, step) >= 0 is the token slot b takes at this step instead of drawing one, -1 leaves the step free.
+ *   free entry: every output is that of lgen_sample_logprob (lgen_sample when logprob_out is null), bit for bit;
+ *   given entry: the noise block is not read; CFG mix and / max(temperature, 1e-5) as always, then no top-k, no top-p, no argmax:
+ *     cur_tok[b] (and cur_tok[B+b]) and seq[b][step] take the given token, and logprob_out[b * seq_stride + step] =
+ *     log_softmax(whole scaled row)[token] -- what lgen_logprob_rows gives for it (a given token may lie outside the kept set).
+ *   Entries are the caller's to validate (< V); the kernel stores token 0 for one that is not.
+ * logprob_out may be null.  LGEN_ERR_BAD_ARG before any launch: given null.  Additive: the ABI version stays 10. */
+int lgen_sample_given(const void* logits, const float* noise, long long noise_step_stride, int* cur_tok, int* seq,
+                      const int* state, int B, int V, int seq_stride, int use_cfg, float cfg_scale, int cfg_interval,
+                      float temperature, int top_k, float top_p, int greedy, int dtype, float* logprob_out, const int* given,
+                      void* stream);
+
 /* Scoring of GIVEN tokens (serve/sampler.py:88-93,119-123 without the filters; the per-token term of the cross-entropy of
  * gpt.py:373-380): out[r] = log_softmax(mix(row r) / max(temperature, 1e-5))[targets[r]], fp32, for r < R.
  *   logits [>= R (+ pair_offset)][V] storage dtype, row-major (what the EPI_ROWS lm_head writes); targets [R] int32; out [R] fp32;
@@ -286,6 +300,14 @@ int lgen_sample_rows_params(const void* logits, const float* noise, int* cur_tok
 int lgen_sample_rows_params_logprob(const void* logits, const float* noise, int* cur_tok, int* seq, int* row_step, int* row_pos,
                                     int max_steps, int B, int V, int seq_stride, int use_cfg, const lgen_slot_sampling* params,
                                     int dtype, float* logprob_out, void* stream);
+
+/* lgen_sample_rows_params_logprob with GIVEN tokens (see lgen_sample_given): given [B][seq_stride] int32, entry (b, row_step[b])
+ * like seq.  A slot at a given entry takes that token, reads no noise, writes the whole-row log-softmax at it, and advances
+ * row_step[b] / row_pos[b] (and row_pos[B+b]) like any other; a slot at -1 is lgen_sample_rows_params_logprob bit for bit; a
+ * skipped slot writes nothing.  LGEN_ERR_BAD_ARG additionally: given null. */
+int lgen_sample_rows_params_given(const void* logits, const float* noise, int* cur_tok, int* seq, int* row_step, int* row_pos,
+                                  int max_steps, int B, int V, int seq_stride, int use_cfg, const lgen_slot_sampling* params,
+                                  int dtype, float* logprob_out, const int* given, void* stream);
 
 /* ---- VQ-VAE tokenizer (tokenizer/tokenizer_image/vq_model.py), fp32 NHWC activations ------------- */
 

@@ -9,5 +9,6 @@ declared in include/lgen.h; importing the package does not need a GPU, running i
 from .gpt import GPT_models, ModelArgs, Transformer, kv_scales_from_caches  # noqa: F401
 from .vq_model import VQ_models, VQModel  # noqa: F401
 from .generate import generate, score  # noqa: F401
+from .given import complete  # noqa: F401
 
-__all__ = ["GPT_models", "VQ_models", "generate", "score", "Transformer", "VQModel", "ModelArgs", "kv_scales_from_caches"]
+__all__ = ["GPT_models", "VQ_models", "generate", "score", "complete", "Transformer", "VQModel", "ModelArgs", "kv_scales_from_caches"]

@@ -62,6 +62,9 @@ SIGNATURES = {
     "lgen_sample_logprob": [_P, _P, _c.c_longlong, _P, _P, _P, _I, _I, _I, _I, _F, _I, _F, _I, _F, _I, _I, _P, _P],
     "lgen_sample_rows_params_logprob": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P],
     "lgen_logprob_rows": [_P, _P, _P, _I, _I, _I, _F, _F, _I, _P],
+    # image completion: the two log-probability samplers + `given` tokens (taken instead of drawn where >= 0)
+    "lgen_sample_given": [_P, _P, _c.c_longlong, _P, _P, _P, _I, _I, _I, _I, _F, _I, _F, _I, _F, _I, _I, _P, _P, _P],
+    "lgen_sample_rows_params_given": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P],
     "lgen_vq_codebook_prep": [_P, _P, _P, _I, _I, _I, _P],
     "lgen_vq_lookup_pqconv": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "lgen_vq_argmin": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],

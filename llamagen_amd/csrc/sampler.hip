@@ -43,7 +43,35 @@ struct SampleArgs {
     // log-probability of the sampled token under the final sampling distribution (serve/sampler.py:88-93,119-123; null: not
     // wanted): logprob[b * seq_stride + step], the slot `seq` writes
     float* logprob;
+    // image completion (null: absent): given[b * seq_stride + step] >= 0 is the token this slot takes at this step instead of
+    // drawing one, -1 leaves the step free; indexed like seq
+    const int* given;
 };
+
+// the token of (slot b, step): fed to the next step through cur_tok (both CFG halves), recorded in seq; the continuous-batching
+// form also advances the slot's step and the positions of its rows
+LGEN_DEV void write_token(const SampleArgs& a, int b, int step, int tok) {
+    a.cur_tok[b] = tok;
+    if (a.use_cfg) a.cur_tok[a.B + b] = tok;
+    a.seq[(size_t)b * a.seq_stride + step] = tok;
+    if (a.row_step) {
+        a.row_step[b] = step + 1;
+        a.row_pos[b] += 1;
+        if (a.use_cfg) a.row_pos[a.B + b] += 1;
+    }
+}
+
+// l[cs][ce] of the thread that owns vocabulary index (cs * SMP_THREADS + tid) * 8 + ce, by compile-time indices (no scratch)
+LGEN_DEV float owned_logit(const float (&l)[2][8], int tok) {
+    const int cs = tok >> 13, ce = tok & 7;
+    float lc = 0.f;
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+            if (s == cs && e == ce) lc = l[s][e];
+    return lc;
+}
 
 // Ownership: thread t owns the 8 consecutive vocabulary entries of slot s at i = (s*1024 + t)*8
 // (s < NS = 2): every wave-level global access is a contiguous 1 KiB (bf16 logits) / 2 KiB (fp32)
@@ -140,6 +168,9 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) {
     const int b = blockIdx.x, V = a.V, B = a.B;
     const int step = a.row_step ? a.row_step[b] : a.state[1];
     if (a.row_step && step >= a.max_steps) return;  // empty / finished slot (uniform over the workgroup)
+    // a given token: one address per workgroup, so every branch on it is uniform, like params[b] below
+    const int gv = a.given ? a.given[(size_t)b * a.seq_stride + step] : -1;
+    const bool fixed = gv >= 0;
     bool guided = a.use_cfg;
     if (a.params) {  // the slot's own record: one 32-byte load at an address that depends on blockIdx.x only, so every branch on
         const lgen_slot_sampling r = a.params[b];  // these values stays uniform over the workgroup
@@ -161,7 +192,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) {
         const int ic = own[s] ? i0 : 0;
         D::ld8(a.logits, (size_t)b * V + ic, l[s]);
         if (mix) D::ld8(a.logits, (size_t)(B + b) * V + ic, lu[s]);
-        if (!a.greedy) {
+        if (!a.greedy && !fixed) {  // a given token draws nothing: its noise block is not read
             const float4* np = a.row_step ? (const float4*)(a.noise + ((size_t)b * a.max_steps + step) * V + ic)
                                           : (const float4*)(a.noise + (size_t)step * a.noise_stride + (size_t)b * V + ic);
             const float4 n0 = np[0], n1 = np[1];
@@ -196,6 +227,28 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) {
     }
     __syncthreads();
     const float rmax = sh_f, rmin = sh_g;
+
+    // 1b. given token: no histogram, top-k, top-p or argmax.  The model still ran (K/V appended, position advanced); the token fed
+    // back is the given one, and its log-probability is the log-softmax of the whole scaled row at it (what lgen_logprob_rows
+    // gives score()): the token may lie outside the kept set, so the sampling distribution cannot rate it.
+    if (fixed) {
+        const int tok = gv < V ? gv : 0;  // (the callers validate; an id past the table must never reach the next embed)
+        float gsum = 0.f;
+#pragma unroll
+        for (int s = 0; s < SMP_NS; ++s)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) gsum += own[s] ? expf(l[s][e] - rmax) : 0.f;
+        gsum = wave_sum(gsum);
+        if (lane == 0) red_f[wv] = gsum;
+        __syncthreads();
+        if (tid == 0) write_token(a, b, step, tok);
+        if (a.logprob && tid == ((tok >> 3) & (SMP_THREADS - 1))) {
+            float tot = 0.f;
+            for (int i = 0; i < SMP_THREADS / 64; ++i) tot += red_f[i];
+            a.logprob[(size_t)b * a.seq_stride + step] = (owned_logit(l, tok) - rmax) - logf(tot);
+        }
+        return;
+    }
 
     // 2. top-k threshold = k-th largest value (strict '<' removal keeps ties, generate.py:35)
     float thr = -INFINITY;  // keep everything
@@ -485,14 +538,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) {
         // a row whose every ratio is NaN (non-finite logits or noise, e.g. a filler row fed uninitialised memory) has no maximum:
         // token 0 instead of the 0x7fffffff sentinel, which the next step's embedding lookup would follow out of bounds
         bi = (unsigned)bi < (unsigned)a.V ? bi : 0;
-        a.cur_tok[b] = bi;
-        if (a.use_cfg) a.cur_tok[B + b] = bi;
-        a.seq[(size_t)b * a.seq_stride + step] = bi;
-        if (a.row_step) {
-            a.row_step[b] = step + 1;
-            a.row_pos[b] += 1;
-            if (a.use_cfg) a.row_pos[B + b] += 1;
-        }
+        write_token(a, b, step, bi);
         if (a.logprob) sel[0] = (unsigned)bi;
     }
     // log p(token) = (l - rmax) - log(tot), from the scaled logit itself (not log(ex / tot): ex underflows long before l - rmax
@@ -501,16 +547,8 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(SampleArgs a) {
     if (a.logprob) {
         __syncthreads();
         const int bi = (int)sel[0];
-        if (tid == ((bi >> 3) & (SMP_THREADS - 1))) {
-            const int cs = bi >> 13, ce = bi & 7;  // bi = (s * SMP_THREADS + tid) * 8 + e
-            float lc = 0.f;
-#pragma unroll
-            for (int s = 0; s < SMP_NS; ++s)
-#pragma unroll
-                for (int e = 0; e < 8; ++e)
-                    if (s == cs && e == ce) lc = l[s][e];
-            a.logprob[(size_t)b * a.seq_stride + step] = (lc - rmax) - logf(tot);
-        }
+        if (tid == ((bi >> 3) & (SMP_THREADS - 1)))  // bi = (s * SMP_THREADS + tid) * 8 + e
+            a.logprob[(size_t)b * a.seq_stride + step] = (owned_logit(l, bi) - rmax) - logf(tot);
     }
 }
 static_assert(SMP_THREADS * 8 == 1 << 13, "the owner of a vocabulary index is decoded with shifts");
@@ -525,11 +563,11 @@ static int sample_impl(const void* logits, const float* noise, long long noise_s
                        const int* state, int B, int V, int seq_stride, int use_cfg, float cfg_scale,
                        int cfg_interval, float temperature, int top_k, float top_p, int greedy, int dtype,
                        int* row_step, int* row_pos, int max_steps, const lgen_slot_sampling* params, float* logprob,
-                       void* stream) {
+                       const int* given, void* stream) {
     if (V > SMP_MAXV || V < 8 || (V & 7) || B < 1) return LGEN_ERR_BAD_ARG;
     if (!params && !greedy && !noise) return LGEN_ERR_BAD_ARG;  // with records `greedy` lives on the device: the caller's contract
     SampleArgs a{logits, noise, noise_step_stride, cur_tok, seq, state, B, V, seq_stride, use_cfg, cfg_scale,
-                 temperature, top_p, cfg_interval, top_k, greedy, row_step, row_pos, max_steps, params, logprob};
+                 temperature, top_p, cfg_interval, top_k, greedy, row_step, row_pos, max_steps, params, logprob, given};
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = (size_t)SMP_MAXV * sizeof(float);
     static unsigned long long attr_set_mask = 0;   // per device
@@ -558,7 +596,7 @@ extern "C" int lgen_sample(const void* logits, const float* noise, long long noi
                            int cfg_interval, float temperature, int top_k, float top_p, int greedy, int dtype,
                            void* stream) {
     return sample_impl(logits, noise, noise_step_stride, cur_tok, seq, state, B, V, seq_stride, use_cfg, cfg_scale, cfg_interval,
-                       temperature, top_k, top_p, greedy, dtype, nullptr, nullptr, 0, nullptr, nullptr, stream);
+                       temperature, top_k, top_p, greedy, dtype, nullptr, nullptr, 0, nullptr, nullptr, nullptr, stream);
 }
 
 // lgen_sample + the sampled token's log-probability (serve/sampler.py:88-93 log_softmax of the final sampling distribution,
@@ -570,7 +608,7 @@ extern "C" int lgen_sample_logprob(const void* logits, const float* noise, long 
                                    float* logprob_out, void* stream) {
     if (!logprob_out) return LGEN_ERR_BAD_ARG;
     return sample_impl(logits, noise, noise_step_stride, cur_tok, seq, state, B, V, seq_stride, use_cfg, cfg_scale, cfg_interval,
-                       temperature, top_k, top_p, greedy, dtype, nullptr, nullptr, 0, nullptr, logprob_out, stream);
+                       temperature, top_k, top_p, greedy, dtype, nullptr, nullptr, 0, nullptr, logprob_out, nullptr, stream);
 }
 
 // Continuous batching form (autoregressive/serve/sampler.py:54-58,106-108: paired cond / uncond sequences, every request at its
@@ -581,7 +619,7 @@ extern "C" int lgen_sample_rows(const void* logits, const float* noise, int* cur
                                 float temperature, int top_k, float top_p, int greedy, int dtype, void* stream) {
     if (!row_step || !row_pos || max_steps < 1) return LGEN_ERR_BAD_ARG;
     return sample_impl(logits, noise, 0, cur_tok, seq, nullptr, B, V, seq_stride, use_cfg, cfg_scale, cfg_interval, temperature,
-                       top_k, top_p, greedy, dtype, row_step, row_pos, max_steps, nullptr, nullptr, stream);
+                       top_k, top_p, greedy, dtype, row_step, row_pos, max_steps, nullptr, nullptr, nullptr, stream);
 }
 
 // Per-request form (serve/sampler.py:54-58,65-83,106-108: one SamplingParams per sequence): lgen_sample_rows with the six sampling
@@ -594,7 +632,7 @@ extern "C" int lgen_sample_rows_params(const void* logits, const float* noise, i
                                        int dtype, void* stream) {
     if (!params || !row_step || !row_pos || max_steps < 1) return LGEN_ERR_BAD_ARG;
     return sample_impl(logits, noise, 0, cur_tok, seq, nullptr, B, V, seq_stride, use_cfg, 1.0f, -1, 1.0f, 0, 1.0f, 0, dtype, row_step,
-                       row_pos, max_steps, params, nullptr, stream);
+                       row_pos, max_steps, params, nullptr, nullptr, stream);
 }
 
 // lgen_sample_rows_params + the sampled token's log-probability under the SLOT's final sampling distribution: logprob_out
@@ -604,7 +642,28 @@ extern "C" int lgen_sample_rows_params_logprob(const void* logits, const float* 
                                                const lgen_slot_sampling* params, int dtype, float* logprob_out, void* stream) {
     if (!params || !row_step || !row_pos || max_steps < 1 || !logprob_out) return LGEN_ERR_BAD_ARG;
     return sample_impl(logits, noise, 0, cur_tok, seq, nullptr, B, V, seq_stride, use_cfg, 1.0f, -1, 1.0f, 0, 1.0f, 0, dtype, row_step,
-                       row_pos, max_steps, params, logprob_out, stream);
+                       row_pos, max_steps, params, logprob_out, nullptr, stream);
+}
+
+// Image completion: lgen_sample_logprob / lgen_sample_rows_params_logprob with `given` ([B][seq_stride] int32, indexed like seq).
+// Slot b at a step whose entry is >= 0 takes that token instead of drawing one (no noise read, no top-k / top-p); -1 samples as
+// the twin entry point does, bit for bit.  logprob_out may be null in the scalar form.
+extern "C" int lgen_sample_given(const void* logits, const float* noise, long long noise_step_stride, int* cur_tok, int* seq,
+                                 const int* state, int B, int V, int seq_stride, int use_cfg, float cfg_scale, int cfg_interval,
+                                 float temperature, int top_k, float top_p, int greedy, int dtype, float* logprob_out,
+                                 const int* given, void* stream) {
+    if (!given) return LGEN_ERR_BAD_ARG;
+    return sample_impl(logits, noise, noise_step_stride, cur_tok, seq, state, B, V, seq_stride, use_cfg, cfg_scale, cfg_interval,
+                       temperature, top_k, top_p, greedy, dtype, nullptr, nullptr, 0, nullptr, logprob_out, given, stream);
+}
+
+extern "C" int lgen_sample_rows_params_given(const void* logits, const float* noise, int* cur_tok, int* seq, int* row_step,
+                                             int* row_pos, int max_steps, int B, int V, int seq_stride, int use_cfg,
+                                             const lgen_slot_sampling* params, int dtype, float* logprob_out, const int* given,
+                                             void* stream) {
+    if (!params || !row_step || !row_pos || max_steps < 1 || !logprob_out || !given) return LGEN_ERR_BAD_ARG;
+    return sample_impl(logits, noise, 0, cur_tok, seq, nullptr, B, V, seq_stride, use_cfg, 1.0f, -1, 1.0f, 0, 1.0f, 0, dtype, row_step,
+                       row_pos, max_steps, params, logprob_out, given, stream);
 }
 
 extern "C" int lgen_advance_state(int* state, void* stream) {

@@ -17,6 +17,7 @@ import torch
 
 from . import _lib as L
 from . import gemm_schedule as S
+from .given import given_prefix_length
 from .gemm_schedule import MODEL_TILE_SCHEDULES, TESTED_TILE_SCHEDULES, TILE_SCHEDULES, tile_schedule_key  # noqa: F401  (the tests name them here)
 
 
@@ -197,6 +198,7 @@ class DecodeEngine:
         self.cur_tok = z(mts * 16, dtype=torch.int32)
         self.seq = z(max_batch, S8 + 8, dtype=torch.int32)
         self.logp = z(max_batch, S8 + 8, dtype=torch.float32)  # log-probability of seq's tokens (written only when asked for)
+        self.given = None            # image completion: int32 shaped like seq, -1 = free (allocated by the first call that brings `given`)
         self.state = z(2, dtype=torch.int32)                 # [pos, step]
         # The decode / prefill attention consults `causal_mask` (the tensor Transformer.setup_caches exposes as
         # model.causal_mask, writable like the reference's, generate.py:154-163) whenever the model is t2i: a caller
@@ -487,29 +489,37 @@ class DecodeEngine:
             L.check(self.lib.lgen_ssq_pack(L.ptr(self.hp), L.ptr(self.ssq), self.MTs, self.d, self.dt, L.stream()), "ssq_pack")
         self.ssq_parts = self.d // 16
 
-    def _sample(self, B, sp, logp=None):
+    def _sample(self, B, sp, logp=None, given=None):
         """CFG mix + top-k + softmax + argmax(p/q) for the token at step = state[1]; q = noise[step].  `logp` (fp32, shaped like
-        `seq`): also the sampled token's log-probability, at the slot `seq` takes the token (serve/sampler.py:88-93,119-123)."""
+        `seq`): also the sampled token's log-probability, at the slot `seq` takes the token (serve/sampler.py:88-93,119-123).
+        `given` (int32, shaped like `seq`): rows whose entry at this step is >= 0 take that token instead of drawing one."""
         greedy = 0 if sp["sample_logits"] else 1
         stride = B * self.V if not greedy else 0
         args = (L.ptr(self.logits), 0 if greedy else L.ptr(self.noise), stride, L.ptr(self.cur_tok),
                 L.ptr(self.seq), L.ptr(self.state), B, self.V, self.seq.shape[1],
                 1 if sp["use_cfg"] else 0, float(sp["cfg_scale"]), int(sp["cfg_interval"]),
                 float(sp["temperature"]), int(sp["top_k"]), float(sp["top_p"]), greedy, self.dt)
-        if logp is None:
+        if logp is not None:
+            assert logp.shape == self.seq.shape and logp.dtype == torch.float32
+        if given is not None:
+            assert given.shape == self.seq.shape and given.dtype == torch.int32
+            L.check(self.lib.lgen_sample_given(*args, L.ptr(logp), L.ptr(given), L.stream()), "lgen_sample_given")
+        elif logp is None:
             L.check(self.lib.lgen_sample(*args, L.stream()), "lgen_sample")
         else:
-            assert logp.shape == self.seq.shape and logp.dtype == torch.float32
             L.check(self.lib.lgen_sample_logprob(*args, L.ptr(logp), L.stream()), "lgen_sample_logprob")
 
     def _logp_of(self, sp):
         return self.logp if sp.get("return_logprobs") else None
 
+    def _given_of(self, sp):
+        return self.given if sp.get("given") else None
+
     def decode_step(self, B, sp):
         """One KV-cached decode step: advance (pos, step); embed(cur_tok) -> L blocks -> logits -> sample."""
         self._embed(self.tok_emb, self.cur_tok, advance=True)
         self._layers_and_logits()
-        self._sample(B, sp, self._logp_of(sp))
+        self._sample(B, sp, self._logp_of(sp), self._given_of(sp))
 
     # ---- t2i prefix (CaptionEmbedder, gpt.py:110-131) ------------------------------------------
     def caption_embed(self, cond: torch.Tensor) -> torch.Tensor:
@@ -579,6 +589,28 @@ class DecodeEngine:
         ws = self._run_sequence(emb)
         last = unpack_act(ws["hp"], ws["R"])[(T - 1) * B2:]
         self._set_residual(last)
+
+    def _given_begin(self, given, B, N):
+        """`given` [B, N] (validated int32) -> the engine's buffer, shaped like `seq`; everything else in it is free (-1)."""
+        if self.given is None:
+            self.given = torch.full_like(self.seq, -1)
+        self.given.fill_(-1)
+        self.given[:B, :N].copy_(given)
+
+    def _prefill_given(self, model, cond_combined, B, P):
+        """Prefix fast path of image completion: the conditioning rows ++ tok_emb[given[:, :P]] (columns every row gives; the
+        unconditional twins are fed the same tokens) through every layer in ONE whole-sequence pass instead of the prefill and P
+        decode steps.  Leaves KV slots 0 .. T+P-1 filled, the last position's residual stream in the decode workspace, its logits
+        in `logits`, state = (T - 1 + P, P) -- where the stepwise form stands when it samples token P -- and seq[:, :P] written."""
+        cond = self._cond_rows(model, cond_combined)
+        B2, T = cond.shape[0], cond.shape[1]
+        fed = self.given[:B, :P].long().repeat(B2 // B, 1)
+        ws = self._run_sequence(torch.cat([cond, self.tok_emb[fed]], dim=1))        # [B2, T + P, d]
+        self._set_residual(unpack_act(ws["hp"], ws["R"])[(T + P - 1) * B2:])
+        self.state[0] = T - 1 + P
+        self.state[1] = P
+        self._final_logits()
+        self.seq[:B, :P].copy_(self.given[:B, :P])
 
     def _cond_rows(self, model, cond):
         """cls_embedding(cond)[:, :T] (gpt.py:341-346): rows of the class table (LabelEmbedder in eval mode, gpt.py:78-83) or the
@@ -707,8 +739,22 @@ class DecodeEngine:
         sampling = bool(sp["sample_logits"])
         if sampling and not prefilled:
             self._noise_begin(N, B, noise_seq)
+        logp = self._logp_of(sp)
+        # image completion (llamagen_amd/given.py): int32 [B, N], -1 = free.  Stepwise form: the sampler takes a given token
+        # instead of drawing one, at any position, with any storage / KV dtype.  Prefix fast path: the P columns every row gives go
+        # through every layer at once (not with the fp8 KV cache -- no whole-sequence kernels -- nor with log-probabilities)
+        given = sp.pop("_given", None)
+        stepwise = sp.pop("_given_stepwise", False)
+        sp["given"] = given is not None
+        P = 0
+        if given is not None:
+            self._given_begin(given, B, N)
+            if not stepwise and self.kv_dtype is None and logp is None:
+                P = given_prefix_length(given)
         # ---- prefill (generate.py:77-86): state = (pos, step) = (T-1, 0) when the first token is sampled
-        if model.model_type == "c2i":
+        if P >= 1:
+            self._prefill_given(model, cond_combined if model.model_type == "t2i" else cond_combined.to(torch.int32), B, P)
+        elif model.model_type == "c2i":
             self._embed(self.cls_emb, cond_combined.to(torch.int32).contiguous())
             self._layers_and_logits()
         else:
@@ -722,17 +768,18 @@ class DecodeEngine:
                 self._prefill_prefix(emb)
                 self.state[0] = T - 1
                 self._final_logits()
-        logp = self._logp_of(sp)
-        self._sample(B, sp, logp)
-        yield 0
+        self._sample(B, sp, logp, self._given_of(sp))
+        yield P
         # ---- decode (generate.py:105-123): every step first advances (pos, step)
         key = (B, N, self._kv_key(), self._mask() is not None, self.fuse_norm, self.use_tile, tuple(sorted(self.tile_shape_override.items())),
                tuple(sorted(self.tile_override.items())),
                tuple(sorted(self.pass_override.items())), sp["use_cfg"], sp["cfg_scale"],
                sp["cfg_interval"], sp["temperature"], sp["top_k"], sp["top_p"], sp["sample_logits"],
                self.noise.data_ptr() if sampling else 0, logp is not None)
-        use_graph = os.environ.get("LGEN_NO_GRAPH") is None and N > 3
-        i = 1
+        if given is not None:   # the step samples through lgen_sample_given: a graph of its own (P is not part of it: the counters live on the device)
+            key += ("given",)
+        i = P + 1     # tokens 0 .. P are in `seq`
+        use_graph = os.environ.get("LGEN_NO_GRAPH") is None and N > 3 and N - i >= 2   # (a capture needs its eager, warming step first)
         if use_graph:
             if i < N:  # first decode step eagerly (also warms every kernel before capture)
                 self.decode_step(B, sp)

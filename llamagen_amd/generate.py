@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import torch
 
+from .given import PREFIX_FAST_PATH, check_given
 from .gpt import kv_cache_refuse
 
 
@@ -18,7 +19,11 @@ from .gpt import kv_cache_refuse
 def generate(model, cond, max_new_tokens, emb_masks=None, cfg_scale=1.0, cfg_interval=-1, **sampling_kwargs):
     """Drop-in generate(): runs the step generator below to completion on the current stream.
     return_logprobs=True (keyword): returns (ids int32 [B, N], logprobs fp32 [B, N]) -- every token's log-probability under the
-    distribution it was drawn from (after CFG mix, temperature, top-k and top-p; serve/sampler.py:88-93,119-123)."""
+    distribution it was drawn from (after CFG mix, temperature, top-k and top-p; serve/sampler.py:88-93,119-123).
+    given=int tensor [B, N] (keyword; image completion): -1 leaves token j of row b free, a value in [0, vocab) fixes it.  The model
+    still runs at a given position; the token written and fed back is the given one, and noise[j] stays token j's draw whether
+    used or not.  The log-probability of a given token is the log-softmax of the CFG-mixed, temperature-scaled row at it (what
+    score() returns), without top-k / top-p.  ValueError before any launch for another shape, dtype or an entry out of range."""
     it = generate_iter(model, cond, max_new_tokens, emb_masks, cfg_scale, cfg_interval, **sampling_kwargs)
     while True:
         try:
@@ -69,6 +74,10 @@ def generate_iter(model, cond, max_new_tokens, emb_masks=None, cfg_scale=1.0, cf
     sample_logits = sampling_kwargs.pop("sample_logits", True)
     return_logprobs = bool(sampling_kwargs.pop("return_logprobs", False))
     noise_seq = sampling_kwargs.pop("_noise_seq", None)  # test hook: inject the Exp(1) draws [N, B, V]
+    given = sampling_kwargs.pop("given", None)
+    # test hook: True = no prefix fast path (every given token through the sampler), False = the fast path where it applies
+    given_stepwise = sampling_kwargs.pop("_given_stepwise", None)
+    given_stepwise = (not PREFIX_FAST_PATH) if given_stepwise is None else bool(given_stepwise)
     # pipeline hook (llamagen_amd/pipeline.py, batches_per_chain > 1): `cond` is the FIRST batch of a chain and these callables
     # yield the conditioning of the batches that share its decode chain.  They are evaluated in the order consecutive reference
     # generate() calls would consume the default generator: labels of batch j, then batch j's N x [n, V] Exp(1) draws, then
@@ -83,6 +92,10 @@ def generate_iter(model, cond, max_new_tokens, emb_masks=None, cfg_scale=1.0, cf
     use_cfg = cfg_scale > 1.0
     prefix = 1 if kind == "c2i" else cond.shape[1]          # conditioning positions in front of the image tokens
     prefilled = False
+    if given is not None:
+        if more_conds:
+            raise ValueError("given with _more_conds: chains of several batches take no given tokens")
+        given = check_given(given, (cond.shape[0], max_new_tokens), model.config.vocab_size)
     if more_conds:
         if noise_seq is not None:
             raise NotImplementedError("_more_conds with injected noise: concatenate the batches and their noise yourself")
@@ -118,6 +131,9 @@ def generate_iter(model, cond, max_new_tokens, emb_masks=None, cfg_scale=1.0, cf
         sp["_noise_seq"] = noise_seq
     if prefilled:
         sp["_noise_prefilled"] = True
+    if given is not None:
+        sp["_given"] = given
+        sp["_given_stepwise"] = given_stepwise
     return (yield from model._engine.generate_iter(model, rows, B, max_new_tokens, masks, sp))
 
 

@@ -38,6 +38,11 @@ slot-indexed buffer (lgen_sample_rows_params_logprob: the same tokens, one more 
 RequestOutput records.  `SamplingParams(best_of=k)` runs k candidates of one request in k slots (seed + j each) and answers with
 the likeliest; the choice is an argmax on the device, nothing waits for it.
 
+Image completion (`submit(..., given=ids)`, llamagen_amd/given.py): a request may fix any of its N tokens.  The tokens travel in a
+slot-indexed `given` buffer next to `seq` (-1 = free; moved with the request on a bucket switch, shared by `best_of` candidates);
+every step samples through lgen_sample_rows_params_given, so a slot at a given entry takes that token instead of drawing one, in the
+same one graph per bucket.  A request still takes N steps (no start at step P from a private prefill).
+
 Every request produces exactly the tokens a batch-of-one `generate()` would with the same noise and sampling values: rows are
 independent through every kernel (tests/test_gpu_serve.py and tests/test_gpu_serve_params.py hold that to the oracle, token for
 token, in fp32).
@@ -55,6 +60,7 @@ import torch
 
 from . import _lib as L
 from .engine import DecodeEngine
+from .given import check_given
 from .gpt import find_multiple, kv_cache_refuse
 
 
@@ -202,6 +208,9 @@ class ContinuousBatcher:
         self.noise = torch.empty(slots, max_new_tokens, self.V, dtype=torch.float32, device=dev) if sample_logits else None
         self.seq = torch.zeros(slots, max_new_tokens, dtype=torch.int32, device=dev)
         self.logp = torch.zeros(slots, max_new_tokens, dtype=torch.float32, device=dev)   # log-probability of seq's tokens
+        # image completion: the tokens a request fixes (-1 = free), read by the sampler at (slot, step) like seq is written
+        self.given = torch.full((slots, max_new_tokens), -1, dtype=torch.int32, device=dev)
+        self._req_given: Dict[int, torch.Tensor] = {}   # queued requests (candidates) that brought given tokens: int32 [N], CPU
         self._cand: Dict[int, tuple] = {}      # candidate id -> (request id, j) of a best_of request
         self._group: Dict[int, list] = {}      # request id -> its candidates' RequestOutputs (None until finished)
         # the constructor's sampling values: what a request that brings no SamplingParams gets
@@ -266,6 +275,7 @@ class ContinuousBatcher:
                 if self.noise is not None:
                     self.noise[t].copy_(self.noise[s])
                 self.seq[t].copy_(self.seq[s])
+                self.given[t].copy_(self.given[s])
                 self.logp[t].copy_(self.logp[s])
                 self.params[t].copy_(self.params[s])
                 self.row_step[t:t + 1].copy_(self.row_step[s:s + 1])
@@ -279,12 +289,14 @@ class ContinuousBatcher:
 
     # ---- requests ---------------------------------------------------------------------------------------------------
     def submit(self, class_label, noise: Optional[torch.Tensor] = None, emb_mask: Optional[torch.Tensor] = None,
-               sampling: Optional[SamplingParams] = None) -> int:
+               sampling: Optional[SamplingParams] = None, given: Optional[torch.Tensor] = None) -> int:
         """Queue one image request; `noise` (optional, [N, V] fp32 Exp(1) draws) replaces the default generator's draw.
         c2i: `class_label` is the class id.  t2i: `class_label` is the caption embedding [T, caption_dim] (left-padded and already
         multiplied by its mask, sample_t2i.py:95-108) and `emb_mask` its [T] validity mask.
         `sampling` (serve/llm.py:141-210) replaces the constructor's sampling values for this request; with a `seed` and no `noise`
-        the request's Exp(1) block comes from a generator of its own, so its tokens do not depend on slot, arrival or neighbours."""
+        the request's Exp(1) block comes from a generator of its own, so its tokens do not depend on slot, arrival or neighbours.
+        `given` (image completion): integer [N], -1 = free, a value in [0, vocab) fixes token j (generate()'s argument for one
+        request); the candidates of a best_of request share it.  The request still takes N steps."""
         if sampling is not None:
             if not isinstance(sampling, SamplingParams):
                 raise TypeError("sampling must be a llamagen_amd.serve.SamplingParams")
@@ -309,6 +321,8 @@ class ContinuousBatcher:
                 raise ValueError("noise given but the batcher was built with sample_logits=False (greedy)")
             if tuple(noise.shape) != (self.N, self.V):
                 raise ValueError(f"noise must be [{self.N}, {self.V}] fp32 Exp(1) draws, got {tuple(noise.shape)}")
+        if given is not None:
+            given = check_given(given, (self.N,), self.V)
         rid = self._next_id
         self._next_id += 1
         if sampling is not None and sampling.best_of > 1:
@@ -322,10 +336,14 @@ class ContinuousBatcher:
                 self._cand[cid] = (rid, j)
                 self._req_sampling[cid] = dataclasses.replace(sampling, best_of=1,
                                                               seed=None if sampling.seed is None else int(sampling.seed) + j)
+                if given is not None:
+                    self._req_given[cid] = given
                 self._queue.append((cid, label, None))
             return rid
         if sampling is not None:   # a side table, not a fourth queue field: the queue entries stay (rid, label, noise)
             self._req_sampling[rid] = sampling
+        if given is not None:      # a side table like the sampling values
+            self._req_given[rid] = given
         self._queue.append((rid, label, noise))
         return rid
 
@@ -341,6 +359,11 @@ class ContinuousBatcher:
         if self.params.is_cuda:   # pinned staging: the copy is enqueued, the host does not wait for it
             rec = rec.pin_memory()
         self.params[b].copy_(rec, non_blocking=True)
+        given = self._req_given.pop(rid, None)
+        if given is None:
+            self.given[b].fill_(-1)
+        else:
+            self.given[b].copy_(given)
         if self.noise is not None:
             if noise is not None:
                 self.noise[b].copy_(noise.to(self.dev))
@@ -384,7 +407,10 @@ class ContinuousBatcher:
         first = dict(use_cfg=self.use_cfg and sp.cfg_scale > 1.0, cfg_scale=sp.cfg_scale, cfg_interval=sp.cfg_interval,
                      temperature=sp.temperature, top_k=sp.top_k, top_p=sp.top_p, sample_logits=sp.sample_logits)
         pe.noise = self.noise[b].view(self.N, 1, self.V) if self.noise is not None else None
-        pe._sample(1, first, pe.logp)   # writes cur_tok[0]; both step-batch rows take it below
+        if pe.given is None:
+            pe.given = torch.full_like(pe.seq, -1)
+        pe.given[0, 0:1].copy_(self.given[b, 0:1])   # column 0 of the request's given tokens: the prefill samples token 0
+        pe._sample(1, first, pe.logp, pe.given)   # writes cur_tok[0]; both step-batch rows take it below
         for src, dst in ((0, b),) + (((1, self.B + b),) if self.use_cfg else ()):
             e.k_cache[:, dst, :, :T].copy_(pe.k_cache[:, src, :, :T])
             e.v_cache[:, dst, :, :T].copy_(pe.v_cache[:, src, :, :T])
@@ -405,10 +431,11 @@ class ContinuousBatcher:
         e.ssq_parts = e.d // 16
         e._layers_and_logits()
         # noise is null only in a batcher built greedy, and submit() lets no sampled request into one (the kernel's contract)
-        L.check(lib.lgen_sample_rows_params_logprob(L.ptr(e.logits), L.ptr(self.noise), L.ptr(e.cur_tok), L.ptr(self.seq),
-                                                    L.ptr(self.row_step), L.ptr(self.row_pos), self.N, self.B, e.V, self.N,
-                                                    1 if self.use_cfg else 0, L.ptr(self.params), e.dt, L.ptr(self.logp),
-                                                    L.stream()), "sample_rows_params_logprob")
+        # always the `given` form (a slot without given tokens holds -1 throughout): one graph per bucket
+        L.check(lib.lgen_sample_rows_params_given(L.ptr(e.logits), L.ptr(self.noise), L.ptr(e.cur_tok), L.ptr(self.seq),
+                                                  L.ptr(self.row_step), L.ptr(self.row_pos), self.N, self.B, e.V, self.N,
+                                                  1 if self.use_cfg else 0, L.ptr(self.params), e.dt, L.ptr(self.logp),
+                                                  L.ptr(self.given), L.stream()), "sample_rows_params_given")
 
     def run(self, use_graph: bool = True, return_outputs: bool = False):
         """Drain the queue; returns {request id: int32 [N] token ids} (device tensors, enqueued on the current stream), with
